@@ -20,7 +20,15 @@ keys plus
                   library on the launch stream during the timed region) vs 8 TB/s; "traffic" = HBM bytes per
                   launch from the committed rocprofv3 --pmc passes ("traffic_profile"), only when those passes were
                   taken on the same kernel sources as the library being timed, else null
-  "roofline_step", "stage_ms": the whole step against 8 TB/s; mean time of every stage (untimed pass, all stages bracketed)
+  "roofline_step", "stage_ms": the whole step against 8 TB/s; mean time per launch of the dominant stage as timed inside
+                  the timed region (--full: of every stage, from an untimed pass with all stages bracketed)
+  "detail":       path of the DETAIL record (JSON) holding everything else: per-step arrays, and with --full the whole
+                  C4 record and every secondary leg with its stage table
+
+A plain run does only what the headline needs: set-up, warm-up, the K timed steps, the outputs of the last step when
+--dump-outputs DIR is given (DIR/<name>.npy, float32: the images in full, every per-Gaussian array on a fixed sample of
+DUMP_ROWS Gaussians), the line.  --full adds every other measurement to the line:
+
   "cpu_baseline": the CPU oracle (a port of the reference algorithm, OpenMP) on the same workload, N = 1 only
   "c4":           summary of BASELINE config C4 -- the 64-view rotate360 sweep of scene B (1 M Gaussians, forward
                   only), STRONG-scaled over the N ranks: sweep time with the Gaussians resident, and cold (one packed
@@ -29,9 +37,9 @@ keys plus
                   every step, BloomScene's real call shape (512^2, anchors x 10 through the fused expansion,
                   colors_precomp, sh_degree 1), and the headline workload in the two bit-for-bit modes
                   (strict gradients, exact exp)
-  "detail":       path of the DETAIL record (JSON) holding everything else: per-step arrays, the whole C4 record, every
-                  secondary leg with its stage table.  --full adds the long legs (180 / 720-view presets, capacity-mode
-                  and HIP-graph legs) and echoes the detail record on stderr; --experimental adds the C4 latency model.
+
+and the long legs (180 / 720-view presets, capacity-mode and HIP-graph legs), the stage table of every stage, and an
+echo of the detail record on stderr; --full --experimental adds the C4 latency model.
 """
 from __future__ import annotations
 
@@ -57,6 +65,11 @@ CONFIGS = {
     "c3": (1_000_000, 1920, 1080, 3, True),
     "c5": (5_000_000, 1920, 1080, 3, True),
 }
+
+# --dump-outputs: per-Gaussian arrays are written for a fixed sample of this many Gaussians (dump_rows), so that the
+# whole dump of a 1920x1080 SH-3 step stays under DUMP_LIMIT_BYTES (33 MB of images + 17 MB of sampled rows)
+DUMP_ROWS = 65_536
+DUMP_LIMIT_BYTES = 64_000_000
 
 
 def algorithmic_bytes(P, M, R, N):
@@ -195,14 +208,17 @@ class Dist:
             dist.destroy_process_group()
 
 
-def timed_steps(D, step, steps, warmup, stage_events=True, dominant=None, prewarm_ms=0.0):
+def timed_steps(D, step, steps, warmup, stage_events=True, dominant=None, prewarm_ms=0.0, stage_table=True,
+                after_timed=None):
     """The contract's timing: W untimed steps, then EXACTLY K steps between barrier + synchronize on both sides, MAX over
     ranks.  Also one torch event per step (on the launch stream) for the median step time.  -> dict.
 
     Inside the timed region only the DOMINANT stage (`dominant`, e.g. "render_bwd") is bracketed by hipEvents, on every
     4th step: an event pair costs ~35 us of pipeline bubble on MI355X, and bracketing all seven stages of every 4th
-    step made the sampled steps 0.26 ms (20 %) longer -- 5 % off the very throughput being measured.  The stage table
-    comes from a short untimed pass after the timed region, every stage of every step bracketed."""
+    step made the sampled steps 0.26 ms (20 %) longer -- 5 % off the very throughput being measured.  With
+    `stage_table`, the stage table comes from a short untimed pass after the timed region, every stage of every step
+    bracketed; without it, only the dominant stage is reported.  `after_timed` runs right after the timed region, before
+    any further step."""
     from bloomscene_amd import _capi
     # the collector runs BEFORE the clock ramp, not between it and the timed region: a full collection is tens of
     # milliseconds of idle GPU, after which the first ten timed steps ran up to 30 % slow (1.68 -> 1.25 ms at C3)
@@ -252,6 +268,8 @@ def timed_steps(D, step, steps, warmup, stage_events=True, dominant=None, prewar
     dt = time.perf_counter() - t0
     gc.enable()
     device_allocs = torch.cuda.memory_stats(D.dev).get("num_device_alloc", 0) - allocs0
+    if after_timed is not None:
+        after_timed()
     host_step_ms = [1e3 * (b - a) for a, b in zip([t0] + host_marks[:-1], host_marks)]
     in_order = [marks[i].elapsed_time(marks[i + 1]) for i in range(steps)]
     per_step = sorted(in_order)
@@ -259,7 +277,9 @@ def timed_steps(D, step, steps, warmup, stage_events=True, dominant=None, prewar
     _capi.profile_enable(False)
     _capi.profile_only(None)
     prof = dict(prof_timed)
-    if events_on and dominant is not None:
+    if events_on and dominant is not None and not stage_table:
+        prof = {k: v for k, v in prof_timed.items() if v[1] > 0}   # (the dominant stage: the others carried no events)
+    elif events_on and dominant is not None:
         # the stage table: an untimed pass with every stage bracketed (its step time is not reported anywhere)
         _capi.profile_enable(1)
         _capi.profile_reset()
@@ -286,11 +306,12 @@ def timed_steps(D, step, steps, warmup, stage_events=True, dominant=None, prewar
 
 
 def raster_workload(D, args, P, W, H, deg, do_bwd, precomp=False, scale_mul=1.0, cycle_views=1, steps=None, warmup=None,
-                    label="c3", allreduce=False, depth_gradient=False, mode="default"):
+                    label="c3", allreduce=False, depth_gradient=False, mode="default", dump=False):
     """fwd(+bwd) steps of the rasterizer on scene A; returns the measurements of this rank (rank 0's are printed).
     ``mode``: "default" (the reference's call: the forward blocks on the read-back of num_rendered); "capacity"
     (GaussianRasterizer(capacity=1.25 R + 4096): BSR_FLAG_NO_READBACK, the host never waits); "graph" (the capacity-mode
-    step captured once into a HIP graph and replayed).  Secondary legs only: the metric is quoted on "default"."""
+    step captured once into a HIP graph and replayed).  Secondary legs only: the metric is quoted on "default".
+    ``dump``: also return the outputs of the last timed step (step_outputs) as "outputs"."""
     from bloomscene_amd import GaussianRasterizationSettings, GaussianRasterizer
     from bloomscene_amd.synthetic import scene_a, upstream_grads
     from bloomscene_amd.views import allreduce_gradients, broadcast_gaussians, yawed_camera
@@ -353,6 +374,7 @@ def raster_workload(D, args, P, W, H, deg, do_bwd, precomp=False, scale_mul=1.0,
             if allreduce and D.multi:
                 state["allreduce_ms"] = state.get("allreduce_ms", 0.0) + allreduce_gradients(leaves, force=D.force)
         state["radii"] = radii
+        state["last"] = (color, depth, means2D)
 
     steps = steps or args.steps
     warmup = args.warmup if warmup is None else warmup
@@ -372,10 +394,12 @@ def raster_workload(D, args, P, W, H, deg, do_bwd, precomp=False, scale_mul=1.0,
         with torch.cuda.graph(graph):
             step()
         eager_step, step = step, graph.replay
+    outputs = {}
     tm = timed_steps(D, step, steps, warmup, dominant="render_bwd" if do_bwd else "render_fwd",
                      prewarm_ms=args.prewarm_ms,   # every leg: the GPU idles while the host builds the leg's scene, and a
                                                    # leg timed on clocks still ramping reads 4-5 % slow (docs/EXPERIMENTS.md)
-                     stage_events=mode != "graph")
+                     stage_events=mode != "graph", stage_table=args.full,
+                     after_timed=(lambda: outputs.update(step_outputs(state, leaves, precomp))) if dump else None)
     if mode == "capacity":
         from bloomscene_amd.rasterizer import check_deferred
         check_deferred()   # (raises if a frame of the timed region overflowed its capacity)
@@ -412,9 +436,44 @@ def raster_workload(D, args, P, W, H, deg, do_bwd, precomp=False, scale_mul=1.0,
                        + (f", camera changes every step ({cycle_views} views, 1 degree apart)" if cycle_views > 1 else "")
                        + ({"default": "", "capacity": "; capacity mode (BSR_FLAG_NO_READBACK: no host wait)",
                            "graph": "; the capacity-mode step replayed from a HIP graph"}[mode])}
+    if dump:
+        res["outputs"] = outputs
     del leaves, bufs, rasterizers
+    state.clear()   # (the last step's outputs: freed before the cache is emptied)
     torch.cuda.empty_cache()
     return res
+
+
+def dump_rows(P):
+    """The Gaussians whose per-Gaussian outputs --dump-outputs writes: all of them up to DUMP_ROWS, else a fixed seeded
+    sample of DUMP_ROWS, in ascending order."""
+    if P <= DUMP_ROWS:
+        return torch.arange(P)
+    return torch.randperm(P, generator=torch.Generator().manual_seed(7))[:DUMP_ROWS].sort().values
+
+
+def step_outputs(state, leaves, precomp):
+    """What a caller of the last step received, as float32 numpy arrays: colour and depth images in full; radii and the
+    gradients of means2D and of every input (colors_precomp in place of shs under --colors precomp) for the dump_rows
+    sample."""
+    color, depth, means2D = state["last"]
+    radii = state["radii"]
+    rows = dump_rows(radii.shape[0]).to(radii.device)
+    per_gaussian = {"radii": radii, "grad_means2D": means2D.grad}
+    for k, v in leaves.items():
+        per_gaussian["grad_" + ("colors_precomp" if precomp and k == "shs" else k)] = v.grad
+    out = {"color": color.detach(), "depth": depth.detach()}
+    out.update({k: v.detach().index_select(0, rows) for k, v in per_gaussian.items() if v is not None})
+    return {k: v.float().cpu().numpy() for k, v in out.items()}
+
+
+def write_outputs(out_dir, arrays):
+    import numpy as np
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_LIMIT_BYTES, f"--dump-outputs: {total} bytes"
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
 
 
 def secondary_line(r):
@@ -757,9 +816,9 @@ def main():
                                                 "diagnostic builds of csrc/Makefile) instead of the in-tree product library")
     ap.add_argument("--lib-older-abi", action="store_true",
                     help="with --lib: accept a build of an earlier ABI version (A/B runs against an earlier round's library)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-c4", action="store_true", help="skip the C4 rotate360 sweep leg")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the secondary (N = 1) workloads")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-c4", action="store_true", help="with --full: skip the C4 rotate360 sweep leg")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip the secondary (N = 1) workloads")
     ap.add_argument("--c4-forms", default="batched", choices=["batched", "all"],
                     help="N > 1: which forms of the visible-subset distribution the C4 leg times -- 'batched' (one pack, all "
                          "sends posted as one group: the default of views.scatter_visible_gaussians) or 'all' (also the "
@@ -772,11 +831,16 @@ def main():
                     help="BSR_FLAG_EXACT_GRAD on every call: the reference's per-pair operations in the backward tile "
                          "walk (meets SURVEY 8(d)'s elementwise gradient bar); the metric is quoted on the default")
     ap.add_argument("--full", action="store_true",
-                    help="also run the long legs (the 180- and 720-view C4 presets, capacity-mode and HIP-graph legs) and "
-                         "echo the detail record on stderr; the contract line on stdout stays compact either way")
+                    help="also measure everything beside the headline: the stage table of every stage, the CPU baseline, "
+                         "the C4 sweep, the secondary workloads and the long legs (the 180- and 720-view C4 presets, "
+                         "capacity-mode and HIP-graph legs), and echo the detail record on stderr; the contract line on "
+                         "stdout stays compact either way")
     ap.add_argument("--experimental", action="store_true",
-                    help="C4 leg: also evaluate the latency model of the visible-subset distribution and (with --c4-forms "
-                         "all) its pipelined forms (bloomscene_amd.experimental; validated on gloo only)")
+                    help="C4 leg (--full): also evaluate the latency model of the visible-subset distribution and (with "
+                         "--c4-forms all) its pipelined forms (bloomscene_amd.experimental; validated on gloo only)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write the outputs of the last timed step as DIR/<name>.npy (float32): colour and depth images, "
+                         "radii and the input gradients of a fixed sample of Gaussians (bench.dump_rows)")
     ap.add_argument("--detail", default="", help="where the detail record (JSON) is written")
     ap.add_argument("--prewarm-ms", type=float, default=300.0,
                     help="untimed steps run for this long BEFORE the W warm-up steps of the headline workload, so that the "
@@ -801,7 +865,9 @@ def main():
                 and not args.allreduce_grads and args.scale_mul == 1.0 and args.cycle_views == 1)
     r = raster_workload(D, args, P, W, H, deg, do_bwd, precomp=precomp, scale_mul=args.scale_mul,
                         cycle_views=args.cycle_views, label=args.config, allreduce=args.allreduce_grads,
-                        depth_gradient=args.depth_gradient)
+                        depth_gradient=args.depth_gradient, dump=bool(args.dump_outputs) and D.rank == 0)
+    if "outputs" in r:
+        write_outputs(args.dump_outputs, r.pop("outputs"))
     leg_failed = [False]
 
     def guarded(fn, *a, **kw):
@@ -827,8 +893,8 @@ def main():
             leg_failed[0] = True
             return err or {"error": "abandoned: this leg failed on another rank"}
         return res
-    c4 = None if args.no_c4 else guarded(c4_sweep, D, args)
-    if c4 is not None and headline and args.full and "error" not in c4:
+    c4 = guarded(c4_sweep, D, args) if args.full and not args.no_c4 else None
+    if c4 is not None and headline and "error" not in c4:
         # the reference's own rotate360 preset: 180 views, 2 degrees apart (utils/trajectory.py:102-126)
         c4_180 = guarded(c4_sweep, D, args, n_views=180, repeats=3)
         keep = ("workload", "views", "views_per_rank", "broadcast_ms", "views_per_call_16", "views_per_call_16_compacted",
@@ -839,7 +905,7 @@ def main():
         c4_720 = guarded(c4_sweep, D, args, n_views=720, repeats=2)
         c4["preset_720_views"] = c4_720 if "error" in c4_720 else {k: c4_720[k] for k in keep if k in c4_720}
     secondary = None
-    if D.world == 1 and headline and not args.no_secondary:
+    if args.full and D.world == 1 and headline and not args.no_secondary:
         sec_steps = max(20, args.steps // 2)
 
         def leg(label, **kw):
@@ -935,7 +1001,7 @@ def main():
         if secondary is not None:
             line["secondary_Msplats_per_s"] = {k: (v.get("value") if isinstance(v, dict) and "value" in v else None)
                                                for k, v in secondary.items() if k != "raster_512_precomp"}
-        if D.world == 1 and not args.no_cpu_baseline:
+        if args.full and D.world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(args, P, W, H, r["deg"], do_bwd, precomp)
         detail = dict(line)
         detail["roofline"] = roofline_detail

@@ -1,6 +1,7 @@
-"""bench.py on the GPU box: the JSON line of the default invocation carries the contract keys, the roofline record,
-the strong-scaled C4 sweep and the secondary workloads; and the N > 1 code path (RCCL broadcast, barriers, gradient
-all-reduce) executes with one rank under torch.distributed.run."""
+"""bench.py on the GPU box: the JSON line of a plain invocation carries the contract keys and the roofline record and
+nothing that takes runs of its own, and --dump-outputs writes what the last timed step computed; with --full the line
+also carries the CPU baseline, the strong-scaled C4 sweep and the secondary workloads; and the N > 1 code path (RCCL
+broadcast, barriers, gradient all-reduce) executes with one rank under torch.distributed.run."""
 import os
 
 import pytest
@@ -46,7 +47,7 @@ def test_bench_rccl_path_on_one_rank():
     rank under torch.distributed.run (BSR_BENCH_FORCE_DIST=1), on a reduced Gaussian count.  8-GPU runs are the driver's;
     this proves the collectives execute on RCCL and the JSON carries the C4 record."""
     d = _run_bench(["--gpus", "1", "--steps", "6", "--warmup", "2", "--gaussians", "200000", "--allreduce-grads",
-                    "--no-cpu-baseline"], env_extra={"BSR_BENCH_FORCE_DIST": "1"}, nproc=1)
+                    "--no-cpu-baseline", "--full"], env_extra={"BSR_BENCH_FORCE_DIST": "1"}, nproc=1)
     assert d["n_gpus"] == 1 and d["value"] > 0
     assert d["config"]["broadcast_ms"] > 0                       # the broadcast really ran
     assert d["config"]["allreduce_ms_per_step"] > 0              # and so did the all-reduce, every step
@@ -70,7 +71,7 @@ def test_bench_several_ranks_control_flow_on_one_gpu(world):
     distribution forms (--experimental --c4-forms all)."""
     extra = ["--experimental", "--c4-forms", "all"] if world == 2 else []
     line, d = _run_bench(["--gpus", str(world), "--steps", "6", "--warmup", "2", "--gaussians", "200000", "--allreduce-grads",
-                          "--no-cpu-baseline"] + extra,
+                          "--no-cpu-baseline", "--full"] + extra,
                          env_extra={"BSR_BENCH_SINGLE_DEVICE": "1", "BSR_BENCH_BACKEND": "gloo"}, nproc=world, want_line=True)
     sv = d["c4"]["scatter_visible"]
     if world == 2:
@@ -95,16 +96,16 @@ def test_bench_launches_its_own_ranks_when_typed_plainly():
     two ranks itself as child processes under torch.distributed.run and relay rank 0's JSON line (round 2: it exited
     with rc 1).  Both ranks on this box's one GPU over gloo, as in the control-flow test above."""
     d = _run_bench(["--gpus", "2", "--steps", "4", "--warmup", "1", "--gaussians", "100000", "--no-cpu-baseline",
-                    "--prewarm-ms", "20"], env_extra={"BSR_BENCH_SINGLE_DEVICE": "1", "BSR_BENCH_BACKEND": "gloo"})
+                    "--prewarm-ms", "20", "--full"], env_extra={"BSR_BENCH_SINGLE_DEVICE": "1", "BSR_BENCH_BACKEND": "gloo"})
     assert d["n_gpus"] == 2 and d["scaling"] == "weak" and d["value"] > 0 and d["steps"] == 4
     assert d["c4"]["n_gpus"] == 2 and d["c4"]["views_per_rank"] == [32, 32]
 
 
 def test_bench_headline_line_has_the_contract_keys():
-    """The default invocation (shortened): the LAST stdout line is a compact (< 4 KB) JSON object with the contract
-    keys, config.workload, roofline and cpu_baseline -- what the driver parses into BENCH_rNN.json -- and the detail
-    record beside it holds the C4 sweep and the secondary workloads."""
-    line, d = _run_bench(["--steps", "8", "--warmup", "2", "--cpu-sample", "20000"], want_line=True)
+    """The --full invocation (shortened): the LAST stdout line is a compact (< 4 KB) JSON object with the contract
+    keys, config.workload, roofline and cpu_baseline, and the detail record beside it holds the C4 sweep and the
+    secondary workloads."""
+    line, d = _run_bench(["--steps", "8", "--warmup", "2", "--cpu-sample", "20000", "--full"], want_line=True)
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
               "vs_baseline", "dtype", "data", "config", "roofline", "roofline_step", "stage_ms", "cpu_baseline"):
         assert k in line, k
@@ -144,6 +145,61 @@ def test_bench_headline_line_has_the_contract_keys():
     assert line["secondary_Msplats_per_s"]["c3_strict_gradients"] == sec["c3_strict_gradients"]["value"]
     assert d["config"]["device_allocs_in_timed_region"] == 0
     assert len(d["step_ms"]) == 8
+
+
+@pytest.mark.fast_exp
+def test_bench_plain_run_times_the_headline_only_and_dumps_its_last_step():
+    """The plain invocation: the contract line of the headline workload and nothing that takes runs of its own (no stage
+    table pass, CPU baseline, C4 sweep or secondary leg); --dump-outputs holds what the step's caller received, equal to
+    a fresh forward + backward of the same seeded inputs through GaussianRasterizer in this process."""
+    import math
+    import tempfile
+    import numpy as np
+    import torch
+    import bench
+    import helpers as Hh
+    from bloomscene_amd import GaussianRasterizationSettings, GaussianRasterizer
+    from bloomscene_amd.synthetic import scene_a, upstream_grads
+    from bloomscene_amd.views import yawed_camera
+    with tempfile.TemporaryDirectory() as tmp:
+        line, d = _run_bench(["--steps", "8", "--warmup", "2", "--dump-outputs", tmp], want_line=True)
+        dumped = {f[:-4]: np.load(os.path.join(tmp, f)) for f in os.listdir(tmp)}
+    assert line["steps"] == 8 and line["warmup"] == 2 and line["ms_per_step"] > 0 and line["dtype"] == "f32"
+    assert line["metric"].startswith("Msplats/s fwd+bwd @1M Gaussians 1920x1080 SH3")
+    assert abs(line["value"] - 1e-3 * 1_000_000 / line["ms_per_step"]) < 0.01 * line["value"]
+    for k in ("cpu_baseline", "c4", "secondary_Msplats_per_s"):
+        assert k not in line, k
+    assert "secondary" not in d and "c4" not in d
+    assert set(line["stage_ms"]) == {"render_bwd"} and line["roofline"]["launches_timed"] == 2
+    assert len(d["step_ms"]) == 8 and d["config"]["device_allocs_in_timed_region"] == 0
+    assert sum(a.nbytes for a in dumped.values()) <= bench.DUMP_LIMIT_BYTES
+    assert all(a.dtype == np.float32 for a in dumped.values())
+    # the same step, computed here
+    P, W, H, deg = 1_000_000, 1920, 1080, 3
+    dev = torch.device("cuda:0")
+    sc = scene_a(P, W, H, deg, seed=0)
+    leaves = {k: getattr(sc, k).to(dev).requires_grad_(True)
+              for k in ("means3D", "scales", "rotations", "opacities", "shs")}
+    cam = yawed_camera(W, H, math.radians(60.0)).to(dev)
+    st = GaussianRasterizationSettings(
+        image_height=H, image_width=W, tanfovx=math.tan(cam.FoVx * 0.5), tanfovy=math.tan(cam.FoVy * 0.5),
+        bg=torch.zeros(3, device=dev), scale_modifier=1.0, viewmatrix=cam.world_view_transform,
+        projmatrix=cam.full_proj_transform, sh_degree=deg, campos=cam.camera_center, prefiltered=False, debug=False)
+    means2D = torch.zeros_like(leaves["means3D"], requires_grad=True)
+    color, radii, depth = GaussianRasterizer(st)(means3D=leaves["means3D"], means2D=means2D,
+                                                opacities=leaves["opacities"], shs=leaves["shs"],
+                                                scales=leaves["scales"], rotations=leaves["rotations"])
+    gC, gD = upstream_grads(W, H, seed=1)
+    torch.autograd.backward((color, depth), (gC.to(dev), gD.to(dev)))
+    rows = bench.dump_rows(P).to(dev)
+    assert set(dumped) == {"color", "depth", "radii", "grad_means2D"} | {"grad_" + k for k in leaves}
+    assert dumped["color"].shape == (3, H, W) and dumped["grad_shs"].shape == (bench.DUMP_ROWS, 16, 3)
+    assert np.array_equal(dumped["radii"], radii[rows].float().cpu().numpy())
+    for k, ref in (("color", color), ("depth", depth)):
+        assert Hh.max_err_over_scale(dumped[k], ref.detach().cpu().numpy()) < 1e-6, k
+    for k, t in dict(leaves, means2D=means2D).items():
+        e = Hh.max_err_over_scale(dumped["grad_" + k], t.grad[rows].cpu().numpy())
+        assert e < 1e-5, (k, e)
 
 
 def test_profile_only_brackets_one_stage():

@@ -248,6 +248,42 @@ def test_algorithmic_byte_model_is_consistent():
     assert abs(bench.step_bytes(P, M, R, N, True) - 1.40e9) / 1.40e9 < 0.01
 
 
+def test_dump_outputs_are_the_last_step_on_a_fixed_sample(tmp_path):
+    """bench.py --dump-outputs: float32 arrays of what the step's caller received -- images in full, per-Gaussian arrays
+    on the same seeded sample in every run -- and a 1920x1080 SH-3 step fits the 64 MB budget."""
+    import bench
+    P, W, H, M = bench.DUMP_ROWS + 1000, 8, 6, 16
+    rows = bench.dump_rows(P)
+    assert torch.equal(rows, bench.dump_rows(P)) and len(rows) == bench.DUMP_ROWS
+    assert bool((rows[1:] > rows[:-1]).all()) and int(rows[-1]) < P
+    assert torch.equal(bench.dump_rows(100), torch.arange(100))
+    g = torch.Generator().manual_seed(3)
+    leaves = {k: torch.zeros(s) for k, s in (("means3D", (P, 3)), ("scales", (P, 3)), ("rotations", (P, 4)),
+                                             ("opacities", (P, 1)), ("shs", (P, M, 3)))}
+    for v in leaves.values():
+        v.grad = torch.randn(v.shape, generator=g)
+    means2D = torch.zeros(P, 3)
+    means2D.grad = torch.randn(P, 3, generator=g)
+    color, depth = torch.rand(3, H, W, generator=g), torch.rand(1, H, W, generator=g)
+    radii = torch.randint(0, 50, (P,), dtype=torch.int32, generator=g)
+    out = bench.step_outputs({"last": (color, depth, means2D), "radii": radii}, leaves, precomp=False)
+    assert set(out) == {"color", "depth", "radii", "grad_means2D", "grad_means3D", "grad_scales", "grad_rotations",
+                        "grad_opacities", "grad_shs"}
+    assert all(a.dtype == np.float32 for a in out.values())
+    assert np.array_equal(out["color"], color.numpy()) and np.array_equal(out["depth"], depth.numpy())
+    assert np.array_equal(out["radii"], radii[rows].float().numpy())
+    assert np.array_equal(out["grad_shs"], leaves["shs"].grad[rows].numpy())
+    assert np.array_equal(out["grad_means2D"], means2D.grad[rows].numpy())
+    bench.write_outputs(str(tmp_path / "d"), out)
+    for k, a in out.items():
+        assert np.array_equal(np.load(tmp_path / "d" / (k + ".npy")), a), k
+    # the headline workload's dump: both images and 63 floats per sampled Gaussian
+    c3 = 4 * (4 * 1920 * 1080 + bench.DUMP_ROWS * (1 + 3 + 3 + 3 + 4 + 1 + 48))
+    assert c3 <= bench.DUMP_LIMIT_BYTES
+    per_row = sum(a.nbytes for k, a in out.items() if k not in ("color", "depth")) // bench.DUMP_ROWS
+    assert per_row == 4 * 63
+
+
 def test_scratch_buffers_die_without_the_cycle_collector():
     """The resize callback must not form a reference cycle with its owner: a cycle kept three scratch tensors
     (hundreds of MB at C3) per call alive until the collector ran, i.e. a hipMalloc per step in steady state."""

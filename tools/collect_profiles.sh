@@ -16,10 +16,10 @@ python -m pytest tests -m gpu -q -s > "$OUT/pytest_gpu.log" 2>&1; tail -1 "$OUT/
 # what the driver runs: the LAST stdout line is the compact contract line, the detail record lies beside it
 python bench.py --gpus 1 --steps 20 --warmup 5 --detail "$OUT/bench_c3_driver_form_detail.json" 2> "$OUT/bench_c3.err" | tail -1 > "$OUT/bench_c3_driver_form.json"
 python bench.py --full --detail "$OUT/bench_c3_full_detail.json" 2>> "$OUT/bench_c3.err" | tail -1 > "$OUT/bench_c3_full.json"
-python bench.py --config c2 --steps 100 --warmup 10 --no-cpu-baseline --no-c4 --detail "$OUT/bench_c2_detail.json" 2>/dev/null | tail -1 > "$OUT/bench_c2.json"
-python bench.py --config c5 --steps 20 --warmup 3 --no-cpu-baseline --no-c4 --detail "$OUT/bench_c5_detail.json" 2>/dev/null | tail -1 > "$OUT/bench_c5.json"
-python bench.py --colors precomp --steps 50 --warmup 5 --no-cpu-baseline --no-c4 --detail "$OUT/bench_c3_precomp_detail.json" 2>/dev/null | tail -1 > "$OUT/bench_c3_precomp_colors.json"
-python bench.py --depth-gradient --steps 50 --warmup 5 --no-cpu-baseline --no-c4 --detail "$OUT/bench_c3_depth_gradient_detail.json" 2>/dev/null | tail -1 > "$OUT/bench_c3_depth_gradient.json"
+python bench.py --full --config c2 --steps 100 --warmup 10 --no-cpu-baseline --no-c4 --detail "$OUT/bench_c2_detail.json" 2>/dev/null | tail -1 > "$OUT/bench_c2.json"
+python bench.py --full --config c5 --steps 20 --warmup 3 --no-cpu-baseline --no-c4 --detail "$OUT/bench_c5_detail.json" 2>/dev/null | tail -1 > "$OUT/bench_c5.json"
+python bench.py --full --colors precomp --steps 50 --warmup 5 --no-cpu-baseline --no-c4 --detail "$OUT/bench_c3_precomp_detail.json" 2>/dev/null | tail -1 > "$OUT/bench_c3_precomp_colors.json"
+python bench.py --full --depth-gradient --steps 50 --warmup 5 --no-cpu-baseline --no-c4 --detail "$OUT/bench_c3_depth_gradient_detail.json" 2>/dev/null | tail -1 > "$OUT/bench_c3_depth_gradient.json"
 python tools/bench_anchors.py 2>/dev/null | tail -1 > "$OUT/bench_anchors.json"
 python tools/parity_report.py c1 c2 c3 c5 dense free_camera precomp lists > "$OUT/parity_report.jsonl" 2>/dev/null
 fi
