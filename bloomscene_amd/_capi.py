@@ -1,5 +1,5 @@
-"""ctypes binding of ``libbloomscene_rast.so`` (C ABI declared in ``include/bloomscene_rast.h`` and
-``include/bloomscene_anchors.h``).
+"""ctypes binding of ``libbloomscene_rast.so`` (C ABI declared in ``include/bloomscene_rast.h``,
+``include/bloomscene_anchors.h`` and ``include/bloomscene_grid.h``).
 
 The library is built in-tree (``bloomscene_amd/csrc/Makefile``, hipcc --offload-arch=gfx950).
 There is deliberately NO fallback: if the shared object is missing or a call fails, this module
@@ -92,6 +92,10 @@ SIGNATURES = {
     "bsr_anchor_render_backward": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int] + [_F] * 6 + [_F, _F, _F]
                                    + [_F, C.c_int, C.c_int, C.c_float, _F, _F, _F, C.c_float, C.c_float]
                                    + [_F] * 3 + [_F] * 5 + [_F] + [_F] * 6 + [C.c_int, C.c_void_p, C.c_uint]),
+    # include/bloomscene_grid.h
+    "bsr_grid_backward_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "bsr_grid_encode_forward": (C.c_int, [C.c_int] * 5 + [_F] * 6 + [C.c_void_p]),
+    "bsr_grid_encode_backward": (C.c_int, [C.c_int] * 5 + [_F] * 7 + [C.c_void_p, C.c_void_p]),
 }
 
 _lib = None
