@@ -1,5 +1,5 @@
 """ctypes binding of ``libbloomscene_rast.so`` (C ABI declared in ``include/bloomscene_rast.h``,
-``include/bloomscene_anchors.h`` and ``include/bloomscene_grid.h``).
+``include/bloomscene_anchors.h``, ``include/bloomscene_grid.h`` and ``include/bloomscene_knn.h``).
 
 The library is built in-tree (``bloomscene_amd/csrc/Makefile``, hipcc --offload-arch=gfx950).
 There is deliberately NO fallback: if the shared object is missing or a call fails, this module
@@ -96,6 +96,9 @@ SIGNATURES = {
     "bsr_grid_backward_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "bsr_grid_encode_forward": (C.c_int, [C.c_int] * 5 + [_F] * 6 + [C.c_void_p]),
     "bsr_grid_encode_backward": (C.c_int, [C.c_int] * 5 + [_F] * 7 + [C.c_void_p, C.c_void_p]),
+    # include/bloomscene_knn.h
+    "bsr_knn_scratch_bytes": (C.c_size_t, [C.c_int]),
+    "bsr_knn_mean_dist": (C.c_int, [C.c_int, _F, _F, C.c_void_p, C.c_void_p]),
 }
 
 _lib = None
