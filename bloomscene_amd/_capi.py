@@ -21,6 +21,8 @@ _F = C.c_void_p  # device pointer
 ABI_VERSION = 4  # BSR_VERSION of include/bloomscene_rast.h this binding was written against
 # use_library(..., allow_older_abi=True): 2 -> 3 only added entry points; 3 -> 4 dropped bsr_set_option / bsr_get_option (not
 # bound here any more) and added flag bits -- every entry point bound below has the same signature in all three
+# (tests/helpers.decode_buffers parses the image-buffer and hist1 layout of ABI 4 only, and the numerics(test_flags=...) bits
+# are unknown flags to an older library: A/B runs against one must do without both)
 OLDER_ABI_ACCEPTED = frozenset({2, 3})
 
 

@@ -11,6 +11,7 @@
 // slab, no atomics) -> k_preprocess_bwd (adds each Gaussian's adjacent rows, then the chain).
 #include "../../include/bloomscene_rast.h"
 #include "common.h"
+#include "launch.h"
 
 #include <cstdarg>
 #include <cstdio>
@@ -177,35 +178,6 @@ static int check_deferred(SyncCache* sc)
 		            kept, sc->pending_capacity, (uint32_t)sc->pinned[3]);
 	return 0;
 }
-
-// ---------------------------------------------------------------- kernels (other translation units)
-void launch_preprocess(const PreArgs& a, bool filter_only, hipStream_t s);
-void launch_mark_visible(int P, const float* means3D, const float* vm, uint8_t* present, hipStream_t s);
-void launch_visible_filter_views(int P, int V, const float* means3D, const float* scales, float scale_modifier,
-                                 const float* rotations, const float* cov3D_precomp, const float* viewmatrices,
-                                 const float* projmatrices, int W, int H, float tan_fovx, float tan_fovy, int* radii,
-                                 const int* group_of_view, int n_groups, uint8_t* group_mask, uint32_t* wg_counts,
-                                 uint32_t* group_counts, hipStream_t s);
-void launch_pack_rows(int R, int P, int n_src, const float* const* src, const int* widths, const int64_t* idx,
-                      int idx_stride, float* dst_packed, float* const* dst_each, hipStream_t s);
-void launch_scans(int n_wg, uint32_t* wg_kept, uint32_t* wg_area, int* flags, uint32_t* hist1, int* host_counts,
-                  hipStream_t s);
-int binning_plan(int P, int T, int capacity, long long kept_hint);
-void launch_binning(int plan, int P, int T, int gx, const int* n_ptr, int capacity, const GeomState& geom, BinElem* elems_a,
-                    BinElem* elems_b, uint32_t* hist, int hist_blocks_max, uint2* tile_range, uint32_t* big_tiles,
-                    int* flags, BinElem** elems_sorted, BinElem** elems_free, int* compact_out, hipStream_t s);
-void launch_sort_tiles(int plan, int T, int n_bound, const int* n_ptr, int capacity, uint2* tile_range,
-                       const uint32_t* big_tiles, const int* flags, const uint32_t* digit_total1, const BinElem* elems,
-                       BinElem* elems_free, uint32_t* point_list, int compact, int force_int, int small_grids, hipStream_t s);
-void launch_render_fwd(int gx, int gy, int n_views, int W, int H, const int* n_ptr, int capacity, const uint2* tile_range,
-                       uint32_t* point_list, int* masks_flag,
-                       const float4* rec, const float* bg, float* final_T, uint32_t* n_contrib, float* out_color,
-                       float* out_depth, bool exact_exp, bool nan_on_overflow, int* pool_ctr, hipStream_t s);
-void launch_render_bwd(int gx, int gy, int W, int H, const uint2* tile_range, const uint32_t* point_list,
-                       const float4* rec, const uint32_t* wg_base, const float* bg, const float* final_T,
-                       const uint32_t* n_contrib, const float* dL_dpix, const float* out_depth, const float* dL_depths,
-                       int* masks_flag, float4* slab, bool strict, int num_rendered, hipStream_t s);
-void launch_preprocess_bwd(const BwdArgs& a, hipStream_t s);
 
 // ---------------------------------------------------------------- errors
 static thread_local char g_err[512] = "";
@@ -468,7 +440,6 @@ static int forward_impl(int V, bsr_alloc_fn geometryBuffer, void* geometry_user,
 	BinState bin;
 	BinElem* elems_sorted = nullptr;
 	BinElem* elems_free = nullptr;
-	int elems_compact = 0;   // the binning wrote 8-byte elements (common.h: load_elem_m)
 	// bins, sorts and renders with scratch sized for `capacity` instances; every kernel takes the real count
 	// from device memory and returns at once if it exceeds the capacity
 	auto run_tail = [&](size_t capacity, bool rerun, long long kept_hint) -> int {
@@ -485,11 +456,11 @@ static int forward_impl(int V, bsr_alloc_fn geometryBuffer, void* geometry_user,
 			HIP_TRY(hipMemsetAsync(img.flags + 4, 0, 2 * sizeof(int), s));
 		}
 		const int* n_ptr = img.flags + 2;
-		const int plan = binning_plan((int)P_rows, T, (int)capacity, kept_hint);
+		const BinPlan plan = binning_plan((int)P_rows, T, (int)capacity, kept_hint);
 		{
 			StageTimer t("binning", s);
 			launch_binning(plan, (int)P_rows, T, gx, n_ptr, (int)capacity, geom, bin.elems_a, bin.elems_b, bin.hist, BSR_HIST_BLOCKS_MAX,
-			               img.tile_range, img.big_tiles, img.flags, &elems_sorted, &elems_free, &elems_compact, s);
+			               img.tile_range, img.big_tiles, img.flags, &elems_sorted, &elems_free, s);
 		}
 		STAGE_CHECK("binning", debug, s);
 		{
@@ -497,7 +468,7 @@ static int forward_impl(int V, bsr_alloc_fn geometryBuffer, void* geometry_user,
 			// (the 256 digit totals of pass 1 lie behind the rows of hist1)
 			const uint32_t* digit_total1 = geom.hist1 + (size_t)256 * (((size_t)n_wg + 7) / 8 * 8);
 			launch_sort_tiles(plan, T, (int)capacity, n_ptr, (int)capacity, img.tile_range, img.big_tiles, img.flags,
-			                  digit_total1, elems_sorted, elems_free, bin.point_list, elems_compact,
+			                  digit_total1, elems_sorted, elems_free, bin.point_list,
 			                  ((flags & BSR_FLAG_TEST_SORT_INT) ? 1 : 0) | ((flags & BSR_FLAG_TEST_SORT_NETWORK) ? 2 : 0),
 			                  (flags & BSR_FLAG_TEST_SMALL_GRIDS) != 0, s);
 		}

@@ -266,7 +266,7 @@ __device__ __forceinline__ uint32_t kept_count(uint32_t area, uint64_t mask)
 	return area > 64u ? area : (uint32_t)__popcll(mask);
 }
 
-// The bucket map of the per-tile bucket-and-rank sort (binning.hip: rank_sort): the depth word read as the float it is,
+// The bucket map of the per-tile bucket-and-rank sort (tile_sort.h: rank_sort): the depth word read as the float it is,
 //     b = min(int((z - z_min) * scale), nb - 1),   scale = (nb - 0.5) / (z_max - z_min)   (0 when all depths are equal or the quotient overflows).
 // Monotone in z whatever the roundings (a - c, x * s with s >= 0 and float -> int are all non-decreasing), and for
 // positive finite floats z is monotone in the depth WORD: buckets in ascending order hold ascending keys.  Linear in

@@ -4,6 +4,7 @@
 // (bsr_gather_rows; torch: one index_select per tensor).
 // HBM-bound: 8 B per gathered float; a wave copies whole rows, consecutive lanes consecutive floats of the row.
 #include "common.h"
+#include "launch.h"
 
 namespace bsr {
 

@@ -8,6 +8,7 @@
 #include "common.h"
 #include "sh.h"
 #include "tile_common.h"
+#include "launch.h"
 
 namespace bsr {
 

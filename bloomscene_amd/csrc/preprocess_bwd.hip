@@ -11,6 +11,7 @@
 // (rasterize_points.cu:154-162 zero-fills everything up front).
 #include "common.h"
 #include "sh.h"
+#include "launch.h"
 
 namespace bsr {
 

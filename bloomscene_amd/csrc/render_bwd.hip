@@ -22,6 +22,7 @@
 //     scattered pass; moving the scatter to the write side made k_preprocess_bwd 23 % faster.)
 // As in the forward pass, a staged batch is first compacted per 8x8 quadrant (tile_common.h).
 #include "tile_common.h"
+#include "launch.h"
 
 namespace bsr {
 

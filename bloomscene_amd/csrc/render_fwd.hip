@@ -20,6 +20,7 @@
 // and no exp: `power < power_cut` (precomputed -ln(255*opacity) minus a margin) proves
 // alpha < 1/255 without evaluating it.  The inner loop is wave-uniform (one ballot per entry).
 #include "tile_common.h"
+#include "launch.h"
 
 namespace bsr {
 

@@ -370,7 +370,7 @@ def decode_buffers(P, W, H, R, geom_t, bin_t, img_t):
     out.final_T = img[off:off + N * 4].view(np.float32); off += _al(N * 4)
     out.n_contrib = img[off:off + N * 4].view(np.uint32); off += _al(N * 4)
     # tile_range[T] = (start, end) of every tile's segment in point_list (the reference's `ranges`); the segments tile
-    # the first `kept` entries, in tile order or in (low tile byte, high tile byte) order (csrc/binning.hip: k_bucket_sort)
+    # the first `kept` entries, in tile order or in (low tile byte, high tile byte) order (csrc/tile_sort.hip: k_bucket_sort)
     rng = img[off:off + T * 8].view(np.uint32).reshape(T, 2).astype(np.int64); off += _al(T * 8)
     out.tile_lo, out.tile_hi = rng[:, 0].copy(), rng[:, 1].copy()
     out.tile_count = out.tile_hi - out.tile_lo

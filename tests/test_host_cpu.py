@@ -156,7 +156,8 @@ def test_shard_views_round_robin_partition():
 
 
 def _bitonic_asc(keys):
-    """Python model of bitonic_sort_asc in bloomscene_amd/csrc/binning.hip (same index maths):
+    """Python model of the global-memory steps of the tile sort's network, merge_mirror_step / merge_stride_step in
+    bloomscene_amd/csrc/tile_sort.h (same index maths):
     all-ascending network, compare-exchanges with an upper index >= n are skipped."""
     k = list(keys)
     n = len(k)

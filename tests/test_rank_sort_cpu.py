@@ -1,4 +1,4 @@
-"""The bucket-and-rank sort of a tile's keys (bloomscene_amd/csrc/binning.hip: rank_sort; the map: common.h:
+"""The bucket-and-rank sort of a tile's keys (bloomscene_amd/csrc/tile_sort.h: rank_sort; the map: common.h:
 rank_sort_shift), restated on the host.
 
 Keys are (depth bits << 32 | Gaussian id), unique within a tile.  The kernel deals them into nb buckets by
@@ -124,7 +124,7 @@ def test_piled_up_depths_are_declined_and_ties_inside_the_cap_are_sorted_by_id()
 
 
 def test_source_still_sorts_the_way_this_test_restates_it():
-    b = open(os.path.join(ROOT, "bloomscene_amd", "csrc", "binning.hip")).read()
+    b = open(os.path.join(ROOT, "bloomscene_amd", "csrc", "tile_sort.h")).read()
     h = open(os.path.join(ROOT, "bloomscene_amd", "csrc", "common.h")).read()
     assert re.search(r"#define BSR_RANK_CAP %d\b" % CAP, b)
     assert "if (lo == 0u || hi >= 0x7f800000u) return false;" in b

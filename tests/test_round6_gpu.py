@@ -1,9 +1,9 @@
 """GPU tests added in round 6.
 
-* the two forms of the second binning pass -- the tile-owned chain and k_bucket_sort (csrc/binning.hip: binning_plan) --
+* the two forms of the second binning pass -- the tile-owned chain and k_bucket_sort (csrc/binning.hip: binning_plan; csrc/tile_sort.hip) --
   produce the same bits in every output of forward + backward, on frames with short lists, with lists of every sort
-  class, with 1 / 2 / 4 parts per bucket; and the product library picks the bucket form on sparse frames, the chain on
-  dense ones,
+  class, with 1 / 2 / 4 parts per bucket; and the product library picks the bucket form on sparse and moderately dense frames, the
+  chain on dense ones,
 * an overflowed BSR_FLAG_NO_READBACK frame is NaN in EVERY output, the accumulated-opacity extension included
   (csrc/render_fwd.hip: final_T / n_contrib of the saved image state),
 * a forward issued during stream capture while the previous no-readback forward's overflow check is pending fails
@@ -115,16 +115,34 @@ def test_both_forms_of_the_second_binning_pass_give_the_same_bits():
         assert product[case] == libs["chain_only"][case], case
 
 
+def _plan_thresholds():
+    """(BSR_BUCKET_MAX_PER_TILE, BSR_BKT_BIG_PER_TILE) as the product is built: the #defines next to binning_plan."""
+    import os
+    import re
+    src = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "bloomscene_amd", "csrc",
+                            "binning.hip")).read()
+    return tuple(int(re.search(r"#define %s (\d+)\b" % name, src).group(1))
+                 for name in ("BSR_BUCKET_MAX_PER_TILE", "BSR_BKT_BIG_PER_TILE"))
+
+
+# a frame in the band of k_bucket_sort<2048, 1>: cluster_lists_1k_4k's 920 tiles with larger splats (scale_mul 12: 639
+# kept instances per tile, 16: 1427)
+BAND_CASES = {"cluster_lists_dense": dict(CASES["cluster_lists_1k_4k"], scale_mul=14.0)}
+
+
 @pytest.mark.parametrize("name,bucket_form", [("sh3", True), ("c2_100k_800x800", True), ("cluster_lists_mixed", True),
-                                               ("lists_gt_1024", False), ("lists_gt_8192", False)])
+                                               ("lists_gt_1024", False), ("lists_gt_8192", False),
+                                               ("cluster_lists_dense", True)])
 def test_product_library_picks_the_binning_form_by_size(name, bucket_form):
-    """Sparse frames (at most 850 kept instances per tile on average, <= 8192 tiles) take k_bucket_sort: their tile
-    segments lie bucket by bucket (low tile byte), inside a bucket part by part; dense frames take the chain: segments
-    in tile order.  Either way the lists are the oracle's (checked by _assert_forward_bit_exact)."""
+    """Frames of up to 8192 tiles with at most BSR_BKT_BIG_PER_TILE (1400) kept instances per tile on average take
+    k_bucket_sort -- with 512- or 1024-key areas up to BSR_BUCKET_MAX_PER_TILE (850) per tile, with 2048-key areas
+    beyond (the cluster_lists_dense case must lie strictly inside that band): their tile segments lie bucket by bucket (low tile
+    byte), inside a bucket part by part; denser frames take the chain: segments in tile order.  Either way the lists are
+    the oracle's (checked by _assert_forward_bit_exact)."""
     import numpy as np
     from test_parity_gpu import _assert_forward_bit_exact
     from bloomscene_amd import numerics
-    c = Hh.make_case(**CASES[name])
+    c = Hh.make_case(**(BAND_CASES[name] if name in BAND_CASES else CASES[name]))
     st, _ = Hh.run_oracle(c, backward=False)
     with numerics(exact_exp=True):
         rs, t, R, radii, gb, bb, ib = _assert_forward_bit_exact(c, st)
@@ -142,7 +160,12 @@ def test_product_library_picks_the_binning_form_by_size(name, bucket_form):
         last_of_bucket[d] = max(last_of_bucket.get(d, -1), int(b.tile_hi[t]))
     ds = sorted(first_of_bucket)
     bucket_order = all(last_of_bucket[a] <= first_of_bucket[c] for a, c in zip(ds[:-1], ds[1:]))
-    assert b.kept <= 850 * T if bucket_form else b.kept > 850 * T
+    small_max, big_max = _plan_thresholds()
+    assert (small_max, big_max) == (850, 1400) and T <= 8192
+    print(f"{name}: T = {T}, kept = {b.kept}, kept / T = {b.kept / T:.1f}")
+    assert b.kept <= big_max * T if bucket_form else b.kept > big_max * T
+    if name in BAND_CASES:
+        assert small_max * T < b.kept < big_max * T   # (the product's own choice of k_bucket_sort<2048, 1>)
     if bucket_form:
         assert bucket_order and (T <= 256 or not tile_order)
     else:
@@ -270,7 +293,7 @@ SORT_CASES = ["sh3", "lists_gt_1024", "lists_gt_8192", "clustered_84k_list", "cl
 
 @pytest.mark.parametrize("name", SORT_CASES)
 def test_network_sort_behind_the_rank_sort_gives_the_same_lists(name):
-    """By default a tile's segment is first offered to the bucket-and-rank sort (csrc/binning.hip: rank_sort), which
+    """By default a tile's segment is first offered to the bucket-and-rank sort (csrc/tile_sort.h: rank_sort), which
     every other forward test therefore exercises; BSR_FLAG_TEST_SORT_NETWORK sends every segment of the call through the
     compare-exchange network it falls back to (binary64 flavour where the depths allow).  Both must produce the oracle's
     lists -- every size class, both forms of the second binning pass -- and the same point_list words."""

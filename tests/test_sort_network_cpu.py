@@ -1,4 +1,4 @@
-"""Host-side model of the tile sort's round-based network (bloomscene_amd/csrc/binning.hip): the index arithmetic
+"""Host-side model of the tile sort's round-based network (bloomscene_amd/csrc/tile_sort.h): the index arithmetic
 of every round is replayed in Python to check that (1) the rounds, as scheduled, sort every input (the network is a
 correct bitonic sort with +infinity pads), (2) the slot swizzle is a bijection of [0, n2), and (3) under the LDS bank
 model of the MI355X guide (ds_read_b64: two groups of 32 lanes, slot mod 32; ds_write_b64: four groups of 16 lanes,
