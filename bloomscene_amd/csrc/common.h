@@ -12,7 +12,9 @@
 
 namespace bsr {
 
-// Private layout of the three scratch buffers (opaque to callers).
+// The three scratch buffers (opaque to callers).  Their layout -- section order and sizes -- is stated once per state,
+// in scratch.h (X::layout; host code, included by api.hip alone).
+struct Carver;
 // Per-Gaussian "splat record": everything the tile kernels gather per list entry, exactly one
 // 64-byte cache line:
 //   q0 = (x, y, -conic.a / 2, -conic.b)   q1 = (-conic.c / 2, power_cut, opacity, depth)   q2 = (r, g, b, 0)
@@ -34,6 +36,7 @@ struct GeomState {
 	ushort4* rect;      // [P] tile rect (xmin, ymin, xmax, ymax); zero area <=> culled
 	uint8_t* clamped;   // [P] bit ch = SH colour channel ch was clamped at 0
 	float* depth;           // [P] view-space depth again, compact: k_emit_scatter needs nothing else of the 64-B record
+	static GeomState layout(Carver& c, size_t P);
 	static size_t bytes(size_t P);
 	static GeomState carve(char* p, size_t P);
 };
@@ -106,6 +109,7 @@ struct BinState {
 	float4* slab;         // [R][9 or 10 floats, tight] the backward's per-instance partial sums (k_render_bwd -> k_preprocess_bwd): the SAME
 	                      //        bytes as elems_a / elems_b, which are dead once the forward has returned
 	uint32_t* hist;       // [256 * BSR_HIST_BLOCKS_MAX] digit-major workgroup histograms, then [256] digit totals
+	static BinState layout(Carver& c, size_t R, bool with_slab);
 	static size_t bytes(size_t R, bool with_slab);
 	static BinState carve(char* p, size_t R, bool with_slab);
 };
@@ -121,6 +125,7 @@ struct ImgState {
 	                       //      [64], [96]: pool counters of k_render_fwd / k_render_bwd_t (pooled_tile below)
 	uint32_t* big_tiles;   // [3][T] tiles with more than 1024 instances, one list per size class (any order):
 	                       //        work lists of the wide sort kernels
+	static ImgState layout(Carver& c, size_t N, size_t T);
 	static size_t bytes(size_t N, size_t T);
 	static ImgState carve(char* p, size_t N, size_t T);
 };
@@ -183,10 +188,10 @@ struct BwdArgs {
 	float* dL_drot;            // [P,4]
 };
 
-// Records the calling thread's error message (read back by bsr_last_error) and returns 1.  api.hip
+// Records the calling thread's error message (read back by bsr_last_error) and returns 1.  host_state.hip
 int fail(const char* fmt, ...);
 
-// One blocking 4-byte device->host read through the calling thread's pinned landing buffer.  api.hip
+// One blocking 4-byte device->host read through the calling thread's pinned landing buffer.  host_state.hip
 int read_u32_blocking(const uint32_t* dev, uint32_t* out, hipStream_t s);
 
 static inline size_t align_up(size_t x, size_t a) { return (x + a - 1) & ~(a - 1); }

@@ -1,4 +1,4 @@
-// The internal launch interface: what api.hip calls and the other translation units define, declared once.
+// The internal launch interface: what api.hip calls and the units that hold the kernels define, declared once.
 #pragma once
 #include "common.h"
 

@@ -351,30 +351,51 @@ def _al(x, a=256):
     return (x + a - 1) // a * a
 
 
-def decode_buffers(P, W, H, R, geom_t, bin_t, img_t):
-    """Peek into the opaque buffers (layout in bloomscene_amd/csrc/api.hip).  Tests only."""
-    geom = geom_t.cpu().numpy()
-    img = img_t.cpu().numpy()
-    out = SimpleNamespace()
+def scratch_offsets(P, W, H):
+    """Section offsets (from the 256-byte aligned start) of the geometry and the image buffer of a P-Gaussian, W x H call,
+    as bloomscene_amd/csrc/scratch.h lays them out (tests/test_scratch_layout_cpu.py holds the two against each other)."""
+    g, i = SimpleNamespace(), SimpleNamespace()
     off = 0
-    out.rec = geom[off:off + P * 64].view(np.float32).reshape(P, 16); off += _al(P * 64)
-    out.inst_offset = geom[off:off + P * 4].view(np.uint32); off += _al(P * 4)
+    g.rec = off; off += _al(P * 64)
+    g.inst_offset = off; off += _al(P * 4)
+    g.wg_kept = off
     off += 2 * _al(((P + 255) // 256) * 4)   # wg_kept, wg_area
+    g.hist1 = off
     off += _al((256 * (((P + 255) // 256 + 7) // 8 * 8) + 512) * 4)   # hist1 (pass-1 histogram) + digit totals + digit bases
-    out.kept_mask = geom[off:off + P * 8].view(np.uint64); off += _al(P * 8)
-    out.rect = geom[off:off + P * 8].view(np.uint16).reshape(P, 4); off += _al(P * 8)
-    out.clamped = geom[off:off + P].copy()
+    g.kept_mask = off; off += _al(P * 8)
+    g.rect = off; off += _al(P * 8)
+    g.clamped = off
     N = W * H
     T = ((W + 15) // 16) * ((H + 15) // 16)
     off = 0
-    out.final_T = img[off:off + N * 4].view(np.float32); off += _al(N * 4)
-    out.n_contrib = img[off:off + N * 4].view(np.uint32); off += _al(N * 4)
+    i.final_T = off; off += _al(N * 4)
+    i.n_contrib = off; off += _al(N * 4)
+    i.tile_range = off; off += _al(T * 8)
+    i.flags = off
+    return g, i
+
+
+def decode_buffers(P, W, H, R, geom_t, bin_t, img_t):
+    """Peek into the opaque buffers (layout in bloomscene_amd/csrc/scratch.h, mirrored by scratch_offsets).  Tests only."""
+    geom = geom_t.cpu().numpy()
+    img = img_t.cpu().numpy()
+    out = SimpleNamespace()
+    g, i = scratch_offsets(P, W, H)
+    out.rec = geom[g.rec:g.rec + P * 64].view(np.float32).reshape(P, 16)
+    out.inst_offset = geom[g.inst_offset:g.inst_offset + P * 4].view(np.uint32)
+    out.kept_mask = geom[g.kept_mask:g.kept_mask + P * 8].view(np.uint64)
+    out.rect = geom[g.rect:g.rect + P * 8].view(np.uint16).reshape(P, 4)
+    out.clamped = geom[g.clamped:g.clamped + P].copy()
+    N = W * H
+    T = ((W + 15) // 16) * ((H + 15) // 16)
+    out.final_T = img[i.final_T:i.final_T + N * 4].view(np.float32)
+    out.n_contrib = img[i.n_contrib:i.n_contrib + N * 4].view(np.uint32)
     # tile_range[T] = (start, end) of every tile's segment in point_list (the reference's `ranges`); the segments tile
     # the first `kept` entries, in tile order or in (low tile byte, high tile byte) order (csrc/tile_sort.hip: k_bucket_sort)
-    rng = img[off:off + T * 8].view(np.uint32).reshape(T, 2).astype(np.int64); off += _al(T * 8)
+    rng = img[i.tile_range:i.tile_range + T * 8].view(np.uint32).reshape(T, 2).astype(np.int64)
     out.tile_lo, out.tile_hi = rng[:, 0].copy(), rng[:, 1].copy()
     out.tile_count = out.tile_hi - out.tile_lo
-    flags = img[off:off + 32].view(np.int32)
+    flags = img[i.flags:i.flags + 32].view(np.int32)
     # R = the reference's num_rendered (sum of rect areas) sizes the buffer; the instances actually
     # kept after exact tile culling (flags[2]) are the first entries of point_list
     out.kept = int(flags[2]) if R > 0 else 0

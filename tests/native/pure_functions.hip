@@ -1,9 +1,11 @@
-// Test-only: the product's PURE device functions, compiled from the product's own headers and run on given inputs, so
-// that the python restatements of tests/test_box_test_cpu.py, test_tile_pool_cpu.py and test_bin_elem_cpu.py are checked
+// Test-only: the product's PURE functions, compiled from the product's own headers and run on given inputs, so
+// that the python restatements of tests/test_box_test_cpu.py, test_tile_pool_cpu.py, test_bin_elem_cpu.py and
+// test_scratch_layout_cpu.py are checked
 // against the code the kernels execute (an edit to box_may_hit, pooled_tile or the element packing would
 // otherwise leave those CPU tests green).  Built by tests/native/Makefile into libbsr_pure_functions.so; driven by
 // tests/test_round6_gpu.py through ctypes.  Nothing here is part of the product library.
 #include "../../bloomscene_amd/csrc/tile_common.h"
+#include "../../bloomscene_amd/csrc/scratch.h"
 
 using namespace bsr;
 
@@ -73,6 +75,24 @@ void pt_rank_sort_buckets(int n, const float* z, float zmin, float zmax, int nb,
 {
 	const float scale = rank_sort_scale(zmin, zmax, nb);
 	for (int i = 0; i < n; i++) out[i] = rank_sort_bucket(z[i], zmin, scale, nb);
+}
+// (host side: no GPU) scratch.h: the three totals, then the offset of every section from a 256-byte aligned base, in
+// the order of the struct members (9 of GeomState, 5 of BinState, 5 of ImgState), then the two slab constants
+void pt_scratch_layout(size_t P, size_t R, int with_slab, size_t N, size_t T, size_t* out)
+{
+	char* const base = (char*)(size_t)(1 << 20);
+	const GeomState g = GeomState::carve(base, P);
+	const BinState b = BinState::carve(base, R, with_slab != 0);
+	const ImgState i = ImgState::carve(base, N, T);
+	const void* const sections[] = {g.rec, g.inst_offset, g.wg_kept, g.wg_area, g.hist1, g.kept_mask, g.rect, g.clamped, g.depth,
+	                                b.point_list, b.elems_a, b.elems_b, b.slab, b.hist,
+	                                i.final_T, i.n_contrib, i.tile_range, i.flags, i.big_tiles};
+	*out++ = GeomState::bytes(P);
+	*out++ = BinState::bytes(R, with_slab != 0);
+	*out++ = ImgState::bytes(N, T);
+	for (const void* p : sections) *out++ = (size_t)((const char*)p - base);
+	*out++ = BSR_SLAB_ROW_BYTES;
+	*out++ = BSR_SLAB_TAIL_BYTES;
 }
 int pt_pooled_grid(int n_tiles) { return pooled_grid(n_tiles); }
 int pt_pool_tiles_per_band(int n_tiles) { return pool_tiles_per_band(n_tiles); }

@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
 """Host-side cost of one rasterizer step (python + ctypes + torch allocator + autograd), measured where the GPU is
 not the limit: the C3 call shape on a SMALL scene (P = 20 000), so that every step's wall time is the host's.
-    python3 tools/host_profile.py [--steps 300] [--profile]
-Prints ms per step of forward, backward and the whole step; --profile adds a cProfile table (top 35 by cumulative time)."""
+    python3 tools/host_profile.py [--steps 300] [--profile] [--lib other_build.so]
+Prints ms per step of forward, backward and the whole step; --profile adds a cProfile table (top 35 by cumulative time);
+--lib measures another build of the library (tools/build_base.sh)."""
 import argparse, cProfile, math, os, pstats, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -15,7 +16,11 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--steps", type=int, default=300)
 ap.add_argument("--gaussians", type=int, default=20000)
 ap.add_argument("--profile", action="store_true")
+ap.add_argument("--lib", default=None)
 a = ap.parse_args()
+if a.lib:
+    from bloomscene_amd import _capi
+    _capi.use_library(a.lib)
 dev = torch.device("cuda", 0)
 W, H, deg = 1920, 1080, 3
 sc = scene_a(a.gaussians, W, H, deg, seed=0)
