@@ -25,8 +25,18 @@
  * they are not supported (the python layers raise NotImplementedError; there is no silent fall-back).
  *
  * Semantics per (point b, level l), restated from GC:100-663 with every fp32 operation in the reference's order
- * (tests/grid_reference.py restates them on the CPU; the forward is bit-equal to it):
- *   pos = x * float(res - 2) + 0.5;  pg = floor(pos);  pos -= pg
+ * (tests/grid_reference.py restates them on the CPU; the forward is bit-equal to it, and tests/test_reference_grid_gpu.py
+ * compares outputs, dy_dx and grad_inputs bit for bit with GC itself, compiled for gfx950 with -ffp-contract=off by
+ * oracle/reference_build.py):
+ *   pos = x * float(res - 2) + 0.5;  pg = floor(pos);  pos -= pg      (GC adds a DOUBLE 0.5 and narrows; here the add is
+ *     fp32.  The same bits for every x in [0, 1]: the product is a non-negative fp32, so below 2^-25 both give 0.5, and
+ *     from 2^-25 up its last bit is at 2^-48 or above, the sum fits 53 bits and the double add is exact: one rounding)
+ *     DEVIATION FROM GC AS NVCC BUILDS IT: pos here is rounded twice (the product, then the sum), GC's source order.  A
+ *     contracting compiler (nvcc's default; hipcc's too) narrows that add to fp32 and fuses it: pos = fma(x, float(res - 2),
+ *     0.5), rounded once.  The two differ by an ulp of pos at some inputs, and where the source-order pos is an integer
+ *     (x = (k + 0.5) / (res - 2) in fp32) floor() then picks the neighbouring cell: dy_dx, constant per cell, differs by whole
+ *     row differences there, out by about ulp(pos) times its slope.  Documented, not matched (as with the knn FMA deviation);
+ *     from pos on, a contracting build of GC and this library differ by rounding only (tests/test_reference_grid_gpu.py).
  *   corner c in 0 .. 2^D - 1: w = prod_d (bit d of c ? pos[d] : 1 - pos[d])  (d ascending),
  *     p[d] = bit d ? min(pg[d] + 1, res - 1) : pg[d];  a corner with some p[d] == 0 or p[d] == res - 1 is EXCLUDED
  *   wn = sum of the included w (c ascending), 1e-9 if it is 0;  wn_re = 1 / wn  (correctly rounded)

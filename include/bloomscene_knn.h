@@ -8,7 +8,8 @@
  * 0 on success, bsr_last_error() on failure, no device allocation (all scratch comes from the caller), no state kept
  * between calls.  Nothing synchronises with the host: the call can be captured into a hipGraph.  No float atomics.
  *
- * Semantics -- a pure function of the input, bit for bit (tests/knn_reference.py restates it on the CPU):
+ * Semantics -- a pure function of the input, bit for bit (tests/knn_reference.py restates it on the CPU;
+ * tests/test_reference_knn_gpu.py compares both with SK itself, compiled for gfx950 by oracle/reference_build.py):
  *   d(i, j)    = (dx*dx + dy*dy) + dz*dz,  dx = p_j.x - p_i.x etc.   fp32, every operation rounded, no contraction
  *   C(i)       = { d(i, j) : j != i, d(i, j) < FLT_MAX }   (NaN, inf and values >= FLT_MAX never count; duplicates
  *                                                          count, as 0)
@@ -19,7 +20,8 @@
  * and is nobody's neighbour.  SK's box pruning is exact, so its result does not depend on its Morton order, box size or
  * bounds (SK:193-198 starts the reduction at the origin); it is this function, except that nvcc contracts SK's
  * distance expressions into FMAs by default, which can move a result by a few ulp (as with the rasterizer's
- * libbsr_oracle_fma floor, this is documented, not matched).
+ * libbsr_oracle_fma floor, this is documented, not matched).  That test asserts: bit-equal to SK compiled with
+ * -ffp-contract=off; within a factor (1 + 2^-23)^6 (twelve roundings) of SK compiled with contraction.
  *
  * Supported: 0 <= P <= BSR_KNN_MAX_P.  P == 0 is a no-op.  (Entry point names carry no digits: the header / ctypes
  * table check of tests/test_host_cpu.py reads names as bsr_[a-z_]+.)

@@ -2,8 +2,9 @@
 
 TEST INFRASTRUCTURE ONLY -- see the header of ``bsr_oracle.c``.  Imported by ``tests/``,
 ``__graft_entry__.smoke()`` and the ``cpu_baseline`` leg of ``bench.py``; never by
-``bloomscene_amd``.  PARITY UNPINNED (the reference has no tests/goldens and cannot be built
-or imported here).
+``bloomscene_amd``.  PARITY UNPINNED (the reference has no tests/goldens, and its rasterizer
+cannot be built or imported without the un-vendored GLM; oracle/_ref holds builds of its
+simple-knn and gridencoder submodules only, see reference_build.py).
 
 The orchestration below restates ``CudaRasterizer::Rasterizer::forward/backward/
 visible_filter/markVisible`` (cuda_rasterizer/rasterizer_impl.cu:141-504) and the torch glue

@@ -35,11 +35,27 @@ def _rows(p, hs, res):
     return index % np.uint32(hs)
 
 
-def _cell(x, hs, res, rows_left):
-    """pos, per-corner weights, inclusion, rows and wn_re of every point (x [N, D] fp32, inside [0, 1])."""
+def pos_fused(x, res):
+    """x * float(res - 2) + 0.5 rounded ONCE to fp32: what a contracting compiler's v_fma_f32 gives (the reference's double
+    0.5 narrows to fp32 without moving a bit, then fuses).  Exact: the product of two fp32 is exact in float64; the sum
+    is rounded to odd in float64 (TwoSum residual), and 53 >= 24 + 2 bits make the final rounding to fp32 a single one."""
+    p = np.asarray(x, F32).astype(np.float64) * float((int(res) - 2) & 0xFFFFFFFF)
+    s = p + 0.5
+    bb = s - p
+    e = (p - (s - bb)) + (0.5 - bb)                      # exact residual of the float64 sum
+    toward = np.where(e > 0, np.inf, -np.inf)
+    other = np.nextafter(s, toward)
+    odd = (s.view(np.int64) & 1) == 1
+    s = np.where((e != 0) & ~odd, other, s)
+    return s.astype(F32)
+
+
+def _cell(x, hs, res, rows_left, pos=None):
+    """pos, per-corner weights, inclusion, rows and wn_re of every point (x [N, D] fp32, inside [0, 1]).  pos: the
+    position before floor() if it is not the specification's x * scale + 0.5 in fp32 (pos_fused)."""
     N, D = x.shape
     scale = F32(float((res - 2) & 0xFFFFFFFF))
-    pos = x * scale + F32(0.5)
+    pos = x * scale + F32(0.5) if pos is None else np.ascontiguousarray(pos, F32)
     pg = np.floor(pos).astype(np.uint32)
     pos = pos - pg.astype(F32)
     ws, oks, rows = [], [], []
@@ -208,9 +224,10 @@ def fixed_point_bound(inputs, offsets, resolutions, n_rows, grad):
     return s64.reshape(n_rows, F), (ulp_half + slack).reshape(n_rows, F), cnt.reshape(n_rows, F)
 
 
-def forward_f64(inputs, embeddings, offsets, resolutions):
+def forward_f64(inputs, embeddings, offsets, resolutions, fused_pos=False):
     """Independent float64 torch twin of the interpolation (output only) -> outputs [L, N, F] (torch, float64,
-    differentiable in inputs if they require grad).  Plain dense / hashed indexing by python ints."""
+    differentiable in inputs if they require grad).  Plain dense / hashed indexing by python ints.  fused_pos: take the
+    fp32 position rounded once (pos_fused: a contracting build) instead of the specification's two roundings."""
     import torch
     x = inputs
     N, D = x.shape
@@ -222,7 +239,10 @@ def forward_f64(inputs, embeddings, offsets, resolutions):
         pos = x * (res - 2) + 0.5
         # the position itself is an fp32 quantity of the spec (pos = x * float(res - 2) + 0.5 in fp32): take its value
         # from fp32, keep the float64 derivative
-        pos32 = (x.detach().float() * float(res - 2) + 0.5).double()
+        if fused_pos:
+            pos32 = torch.from_numpy(pos_fused(x.detach().float().numpy(), res)).double()
+        else:
+            pos32 = (x.detach().float() * float(res - 2) + 0.5).double()
         pos = pos + (pos32 - pos.detach())
         pg = torch.floor(pos).detach()
         fr = pos - pg
