@@ -9,7 +9,7 @@
 //   binning alloc (sized from the previous call) -> k_emit_scatter (= first radix pass) -> k_tile_count ->
 //   k_tile_starts -> k_tile_scatter (tile ids of up to 16 bits; else the remaining radix passes -> k_tile_ranges)
 //   -> k_sort_tiles_* (per-tile LDS sort) -> k_render_fwd.  No float atomics anywhere.
-// Backward (rasterizer_impl.cu:403-504): k_render_bwd (per-instance partial sums to a Gaussian-major
+// Backward (rasterizer_impl.cu:403-504): k_render_bwd_t or k_render_bwd_strict (per-instance partial sums to a Gaussian-major
 // slab, no atomics) -> k_preprocess_bwd (adds each Gaussian's adjacent rows, then the chain).
 #include "../../include/bloomscene_rast.h"
 #include "common.h"
@@ -567,9 +567,14 @@ int bsr_backward_ex(int P, int D, int M, int R, const float* background, int wid
 	if (R > 0) {
 		{
 			StageTimer t("render_bwd", s);
-			launch_render_bwd(gx, gy, width, height, img.tile_range, bin.point_list, geom.rec, geom.wg_kept, background, img.final_T,
-			                  img.n_contrib, dL_dpix, out_depth, out_depth ? dL_depths : nullptr, img.flags + 6, slab,
-			                  (flags & BSR_FLAG_EXACT_GRAD) != 0, R, s);
+			RenderBwdArgs w;
+			w.gx = gx; w.gy = gy; w.W = width; w.H = height;
+			w.tile_range = img.tile_range; w.point_list = bin.point_list; w.rec = geom.rec; w.wg_base = geom.wg_kept;
+			w.bg = background; w.final_T = img.final_T; w.n_contrib = img.n_contrib; w.dL_dpix = dL_dpix;
+			w.out_depth = out_depth; w.dL_depths = out_depth ? dL_depths : nullptr;
+			w.masks_flag = img.flags + 6; w.slab = slab;
+			w.strict = (flags & BSR_FLAG_EXACT_GRAD) != 0; w.capacity = R;
+			launch_render_bwd(w, s);
 		}
 		STAGE_CHECK("render_bwd", debug, s);
 	}

@@ -47,7 +47,7 @@ struct BinElem {
 	uint32_t y;   // Gaussian id
 	uint32_t z;   // bits of the view-space depth
 };
-// Slab rows (k_render_bwd -> k_preprocess_bwd) are TIGHT: 9 floats per kept instance (10 with the depth-gradient
+// Slab rows (the backward walks -> k_preprocess_bwd) are TIGHT: 9 floats per kept instance (10 with the depth-gradient
 // extension), 4-byte aligned, moved with wide accesses that only assume that alignment.
 typedef float bsr_f32x4 __attribute__((ext_vector_type(4)));
 typedef float bsr_f32x2 __attribute__((ext_vector_type(2)));
@@ -106,7 +106,7 @@ struct BinState {
 	                      //     k_render_fwd has staged an entry (one view, ids < 2^24, split lists): id | half mask << 24
 	BinElem* elems_a;     // [R] (tile id, gaussian id, depth bits): ping-pong buffers of the radix passes
 	BinElem* elems_b;       // [R]
-	float4* slab;         // [R][9 or 10 floats, tight] the backward's per-instance partial sums (k_render_bwd -> k_preprocess_bwd): the SAME
+	float4* slab;         // [R][9 or 10 floats, tight] the backward's per-instance partial sums (the backward walks -> k_preprocess_bwd): the SAME
 	                      //        bytes as elems_a / elems_b, which are dead once the forward has returned
 	uint32_t* hist;       // [256 * BSR_HIST_BLOCKS_MAX] digit-major workgroup histograms, then [256] digit totals
 	static BinState layout(Carver& c, size_t R, bool with_slab);
@@ -121,7 +121,7 @@ struct ImgState {
 	                       //     (low tile byte, high tile byte) order: nobody reads across a segment's ends
 	int* flags;            // [BSR_FLAGS_BYTES / 4]: prefiltered violation | #tiles (1024, 4096] | kept instances | rect tiles (= reference
 	                       //      num_rendered) | #tiles (4096, 8192] | #tiles > 8192 | point_list words carry the forward's
-	                       //      per-half box tests in their top byte (k_render_fwd -> k_render_bwd*) | - | ... |
+	                       //      per-half box tests in their top byte (k_render_fwd -> k_render_bwd_t) | - | ... |
 	                       //      [64], [96]: pool counters of k_render_fwd / k_render_bwd_t (pooled_tile below)
 	uint32_t* big_tiles;   // [3][T] tiles with more than 1024 instances, one list per size class (any order):
 	                       //        work lists of the wide sort kernels
@@ -171,7 +171,7 @@ struct BwdArgs {
 	const float* campos;
 	float tan_fovx, tan_fovy, focal_x, focal_y;
 	GeomState geom;
-	const float4* slab;            // [R][9 floats; 10 with depth_grad] per-instance partial sums written by k_render_bwd, Gaussian-major:
+	const float4* slab;            // [R][9 floats; 10 with depth_grad] per-instance partial sums written by the backward walks, Gaussian-major:
 	                               //        row wg_base[g/256] + inst_offset[g] + k = k-th kept tile of Gaussian g
 	int depth_grad;                // extension: slab rows carry a tenth float, dL/d(view z), added to dL_dmean3D
 	const int* kept_ptr;           // flags[2] of the forward: kept tile instances (device)

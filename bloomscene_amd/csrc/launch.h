@@ -15,6 +15,25 @@ struct BinPlan {
 	int area, compact;
 };
 
+// One backward tile walk (host side only: the kernels take these as individual arguments).
+struct RenderBwdArgs {
+	int gx, gy, W, H;
+	const uint2* tile_range;
+	const uint32_t* point_list;
+	const float4* rec;
+	const uint32_t* wg_base;
+	const float* bg;
+	const float* final_T;
+	const uint32_t* n_contrib;
+	const float* dL_dpix;
+	const float* out_depth;   // the depth-gradient extension: both or neither
+	const float* dL_depths;
+	int* masks_flag;          // forward's hand-over word (flags[6]; flags[2] = kept instances)
+	float4* slab;             // [capacity][9 or 10 floats]
+	bool strict;              // BSR_FLAG_EXACT_GRAD: k_render_bwd_strict instead of k_render_bwd_t
+	int capacity;             // the R the call was handed
+};
+
 void launch_preprocess(const PreArgs& a, bool filter_only, hipStream_t s);
 void launch_mark_visible(int P, const float* means3D, const float* vm, uint8_t* present, hipStream_t s);
 void launch_visible_filter_views(int P, int V, const float* means3D, const float* scales, float scale_modifier,
@@ -37,10 +56,8 @@ void launch_render_fwd(int gx, int gy, int n_views, int W, int H, const int* n_p
                        uint32_t* point_list, int* masks_flag,
                        const float4* rec, const float* bg, float* final_T, uint32_t* n_contrib, float* out_color,
                        float* out_depth, bool exact_exp, bool nan_on_overflow, int* pool_ctr, hipStream_t s);
-void launch_render_bwd(int gx, int gy, int W, int H, const uint2* tile_range, const uint32_t* point_list,
-                       const float4* rec, const uint32_t* wg_base, const float* bg, const float* final_T,
-                       const uint32_t* n_contrib, const float* dL_dpix, const float* out_depth, const float* dL_depths,
-                       int* masks_flag, float4* slab, bool strict, int num_rendered, hipStream_t s);
+void launch_render_bwd(const RenderBwdArgs& a, hipStream_t s);          // render_bwd.hip: dispatches on a.strict
+void launch_render_bwd_strict(const RenderBwdArgs& a, hipStream_t s);   // render_bwd_strict.hip
 void launch_preprocess_bwd(const BwdArgs& a, hipStream_t s);
 
 }  // namespace bsr

@@ -205,7 +205,7 @@ __global__ void __launch_bounds__(256, (ROW_F4 == 12 ? 6 : 4)) k_preprocess_bwd(
 	constexpr int STAGE_F4 = (ROW_F4 > 0 && 32 * (ROW_F4 + 1) > 192) ? 32 * (ROW_F4 + 1) : 192;   // float4 per wave
 	__shared__ float4 s_stage[4][STAGE_F4];   // ROW_F4 > 0: reinterpreted as ShTile<ROW_F4, 32> by the SH part below
 	float g[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-	float g_z = 0.f;   // dL/d(view z): written only by the depth-gradient variant of k_render_bwd (else 0)
+	float g_z = 0.f;   // dL/d(view z): written only by the depth-gradient variants of the backward walks (else 0)
 	{
 		// rows are tight: 9 floats (10 with the depth gradient), so a run starts on a 4-byte boundary only
 		const uint32_t rowf = (uint32_t)slab_row_floats(a.depth_grad != 0);

@@ -1,412 +1,11 @@
-// Backward tile renderer: back-to-front re-traversal producing, per list entry (= per
-// (tile, Gaussian) instance), the nine partial sums dL/d(mean2D.xy, conic.xyw, opacity, colour.rgb).
+// Backward tile renderer: back-to-front re-traversal producing, per list entry (= per (tile, Gaussian) instance), the
+// nine partial sums dL/d(mean2D.xy, conic.xyw, opacity, colour.rgb) as one row of the Gaussian-major slab that
+// k_preprocess_bwd adds up (no global atomics: render_bwd_strict.hip says why).  Semantics: reference renderCUDA
+// (backward), cuda_rasterizer/backward.cu:399-586 of its depth-diff-gaussian-rasterization submodule; dL_depths is
+// ignored exactly as there (:457-463,539-554 are commented out) unless the depth-gradient extension is asked for.
+// This unit holds the default walk and launch_render_bwd; BSR_FLAG_EXACT_GRAD runs k_render_bwd_strict
+// (render_bwd_strict.hip), the reference's per-pair operations in the reference's order.
 //
-// Semantics: reference renderCUDA (backward), cuda_rasterizer/backward.cu:399-586 (under
-// /root/reference/submodules/depth-diff-gaussian-rasterization); dL_depths is ignored exactly as
-// there (:457-463,539-554 are commented out).  Per (pixel, Gaussian) pair the nine contributions
-// are computed with the reference's operation order.
-//
-// The reference issues 9 lane-scattered float atomicAdds per pair.  On MI355X lane-scattered
-// global float atomics run ~17x below the contiguous rate (~20 G/s chip-wide), which would cap this
-// kernel at ~2 ms for C3.  Instead NO global atomic is issued at all:
-//   * the 9 partials are summed over the wave's 64 pixels by a halving reduction on lane-masked DPP
-//     writes (wave_sums_masked below),
-//   * each wave stores its sums in its own LDS slot (LDS float atomics cost ~16 cycles each on
-//     gfx950 whatever the exec mask); the 4 slots are added in a fixed order at the batch end,
-//   * each instance's 9 sums are written ONCE to its row [9 floats; 10 with the depth gradient] of a GAUSSIAN-MAJOR slab: the
-//     rows of one Gaussian (one per kept tile of its rect, row-major) are adjacent, at the instance
-//     numbering fixed by the forward's preprocess,
-//   * k_preprocess_bwd later reads each Gaussian's rows as one contiguous run and adds them in that
-//     fixed order.  (An earlier version wrote rows in list order and gathered them through an
-//     instance->slot map: 48-B rows fetched at random cost 1.75 sectors each and the map another
-//     scattered pass; moving the scatter to the write side made k_preprocess_bwd 23 % faster.)
-// As in the forward pass, a staged batch is first compacted per 8x8 quadrant (tile_common.h).
-#include "tile_common.h"
-#include "launch.h"
-
-namespace bsr {
-
-// ---- halving reduction of 9 (10) values over the 64 lanes: lane-masked DPP writes ------------
-// Nine independent 6-step reductions would be 54 cross-lane adds.  Instead the values are split
-// between partner lanes at every step, halving the live set; a first version selected the kept value
-// per lane (2 selects + 1 DPP add per pair, 33 instructions).  Measured on MI355X
-// (tools/microbench/valu_rates.hip, 8 waves/SIMD): v_fma/v_mul issue every ~2.6 cycles per SIMD, but
-// v_cndmask (SGPR mask), v_cmp -> SGPR and every DPP add every ~4.3.  So the halving steps run over the lane
-// bits whose DPP writes the hardware can mask -- bit 2 and 3 through bank_mask (banks of 4 lanes),
-// bit 4 and 5 through v_permlane16/32_swap of a PAIR (swap, then one add) -- so a pair-step costs 2
-// instructions and no select; the plain steps over bits 0 and 1 come last, on the single survivor.
-// 24 instructions for 9 values (25 for 10) instead of 33 (35), in place in the input registers.
-// Which lane ends with which component is not assumed: calibrate_components() runs the reduction once
-// on constants and reads the mapping off the result.
-// All ten values are declared in/out so that no two of them can be given the same register (two inputs
-// holding the same SSA value otherwise could, and the block overwrites x0..x3, x8 in place).
-// Hazards: inline asm gets no automatic wait states; a DPP/permlane read needs 2 after a VALU write
-// of the same VGPR -- the order below keeps >= 2 instructions between, s_nop where it cannot.
-template <bool TEN>
-__device__ __forceinline__ float wave_sums_masked(float x0, float x1, float x2, float x3, float x4, float x5, float x6,
-                                                  float x7, float x8, float x9)
-{
-	float t;
-	if (TEN) {
-		asm volatile(
-		    "s_nop 1\n"
-		    "v_add_f32_dpp %0, %0, %0 row_ror:4 row_mask:0xf bank_mask:0x5\n"
-		    "v_add_f32_dpp %1, %1, %1 row_ror:4 row_mask:0xf bank_mask:0x5\n"
-		    "v_add_f32_dpp %2, %2, %2 row_ror:4 row_mask:0xf bank_mask:0x5\n"
-		    "v_add_f32_dpp %3, %3, %3 row_ror:4 row_mask:0xf bank_mask:0x5\n"
-		    "v_add_f32_dpp %4, %4, %4 row_ror:4 row_mask:0xf bank_mask:0x5\n"
-		    "v_add_f32_dpp %0, %6, %6 row_ror:4 row_mask:0xf bank_mask:0xa\n"
-		    "v_add_f32_dpp %1, %7, %7 row_ror:4 row_mask:0xf bank_mask:0xa\n"
-		    "v_add_f32_dpp %2, %8, %8 row_ror:4 row_mask:0xf bank_mask:0xa\n"
-		    "v_add_f32_dpp %3, %9, %9 row_ror:4 row_mask:0xf bank_mask:0xa\n"
-		    "v_add_f32_dpp %4, %10, %10 row_ror:4 row_mask:0xf bank_mask:0xa\n"
-		    "v_add_f32_dpp %0, %0, %0 row_ror:8 row_mask:0xf bank_mask:0x3\n"
-		    "v_add_f32_dpp %1, %1, %1 row_ror:8 row_mask:0xf bank_mask:0x3\n"
-		    "v_add_f32_dpp %0, %2, %2 row_ror:8 row_mask:0xf bank_mask:0xc\n"
-		    "v_add_f32_dpp %1, %3, %3 row_ror:8 row_mask:0xf bank_mask:0xc\n"
-		    "v_add_f32_dpp %4, %4, %4 row_ror:8 row_mask:0xf bank_mask:0xf\n"
-		    "v_mov_b32 %5, %4\n"
-		    "v_permlane16_swap_b32 %0, %1\n"
-		    "v_add_f32 %0, %0, %1\n"
-		    "v_permlane16_swap_b32 %4, %5\n"
-		    "v_add_f32 %4, %4, %5\n"
-		    "s_nop 1\n"
-		    "v_permlane32_swap_b32 %0, %4\n"
-		    "v_add_f32 %0, %0, %4\n"
-		    "s_nop 1\n"
-		    "v_add_f32_dpp %0, %0, %0 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n"
-		    "s_nop 1\n"
-		    "v_add_f32_dpp %0, %0, %0 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n"
-		    : "+v"(x0), "+v"(x1), "+v"(x2), "+v"(x3), "+v"(x8), "=&v"(t), "+v"(x4), "+v"(x5), "+v"(x6), "+v"(x7), "+v"(x9));
-	} else {
-		asm volatile(
-		    "s_nop 1\n"
-		    "v_add_f32_dpp %0, %0, %0 row_ror:4 row_mask:0xf bank_mask:0x5\n"
-		    "v_add_f32_dpp %1, %1, %1 row_ror:4 row_mask:0xf bank_mask:0x5\n"
-		    "v_add_f32_dpp %2, %2, %2 row_ror:4 row_mask:0xf bank_mask:0x5\n"
-		    "v_add_f32_dpp %3, %3, %3 row_ror:4 row_mask:0xf bank_mask:0x5\n"
-		    "v_add_f32_dpp %0, %6, %6 row_ror:4 row_mask:0xf bank_mask:0xa\n"
-		    "v_add_f32_dpp %1, %7, %7 row_ror:4 row_mask:0xf bank_mask:0xa\n"
-		    "v_add_f32_dpp %2, %8, %8 row_ror:4 row_mask:0xf bank_mask:0xa\n"
-		    "v_add_f32_dpp %3, %9, %9 row_ror:4 row_mask:0xf bank_mask:0xa\n"
-		    "v_add_f32_dpp %4, %4, %4 row_ror:4 row_mask:0xf bank_mask:0xf\n"
-		    "v_add_f32_dpp %0, %0, %0 row_ror:8 row_mask:0xf bank_mask:0x3\n"
-		    "v_add_f32_dpp %1, %1, %1 row_ror:8 row_mask:0xf bank_mask:0x3\n"
-		    "v_add_f32_dpp %0, %2, %2 row_ror:8 row_mask:0xf bank_mask:0xc\n"
-		    "v_add_f32_dpp %1, %3, %3 row_ror:8 row_mask:0xf bank_mask:0xc\n"
-		    "v_add_f32_dpp %4, %4, %4 row_ror:8 row_mask:0xf bank_mask:0xf\n"
-		    "v_mov_b32 %5, %4\n"
-		    "v_permlane16_swap_b32 %0, %1\n"
-		    "v_add_f32 %0, %0, %1\n"
-		    "v_permlane16_swap_b32 %4, %5\n"
-		    "v_add_f32 %4, %4, %5\n"
-		    "s_nop 1\n"
-		    "v_permlane32_swap_b32 %0, %4\n"
-		    "v_add_f32 %0, %0, %4\n"
-		    "s_nop 1\n"
-		    "v_add_f32_dpp %0, %0, %0 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n"
-		    "s_nop 1\n"
-		    "v_add_f32_dpp %0, %0, %0 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n"
-		    : "+v"(x0), "+v"(x1), "+v"(x2), "+v"(x3), "+v"(x8), "=&v"(t), "+v"(x4), "+v"(x5), "+v"(x6), "+v"(x7));
-	}
-	(void)t;
-	return x0;
-}
-
-// Component (0..NV-1) whose wave total this lane holds after wave_sums_masked, and whether this lane is
-// the one that stores it (the lowest lane holding that component).  Sums of small integers are exact.
-template <bool TEN>
-__device__ __forceinline__ int calibrate_components(int lane, bool& stores)
-{
-	const float r = wave_sums_masked<TEN>(0.f, 1.f, 2.f, 3.f, 4.f, 5.f, 6.f, 7.f, 8.f, 9.f);
-	const int comp = (int)(r * (1.0f / 64.0f));
-	stores = false;
-#pragma unroll
-	for (int c = 0; c < (TEN ? 10 : 9); c++) {
-		const uint64_t m = wave_ballot(comp == c);
-		if (comp == c) stores = (m != 0ull) && (lane == (int)__builtin_ctzll(m));
-	}
-	return comp;
-}
-
-// Index of this tile's instance of a Gaussian in the Gaussian-major order of KEPT instances (its
-// block starts at inst_offset and enumerates the kept tiles of its rect row-major), from q3 / q2.w of
-// the splat record.
-__device__ __forceinline__ uint32_t instance_index(const uint32_t* __restrict__ wg_base, uint32_t id, const float4 q2,
-                                                   const float4 q3, int tx, int ty)
-{
-	const uint32_t off = wg_base[id >> 8] + __float_as_uint(q3.x), lo = __float_as_uint(q3.y), wh = __float_as_uint(q3.z);
-	const uint32_t xmin = lo & 0xffffu, ymin = lo >> 16, w = wh & 0xffffu, h = wh >> 16;
-	const uint64_t mask = ((uint64_t)__float_as_uint(q2.w) << 32) | (uint64_t)__float_as_uint(q3.w);
-	const uint32_t k = ((uint32_t)ty - ymin) * w + ((uint32_t)tx - xmin);
-	return off + kept_rank(w * h, mask, k);
-}
-
-// ---- k_render_bwd_strict: BSR_FLAG_EXACT_GRAD ----------------------------------------------------------------------
-// The reference's per-pair operations on the reference's operands (backward.cu:521,527-536,557,561-583): IEEE
-// divisions, no fp contraction, the pinned exp on every pair, accum_rec channel by channel, the per-pair terms summed as
-// they are -- only the ORDER of the nine sums then differs from the oracle's.  The nine values of a visit are summed over
-// the wave by the masked DPP network above and filed per wave; 128-entry batches staged by waves 0 and 1
-// (stage_and_compact).  Until round 4 this walk (with the arithmetic shortcuts of k_render_bwd_t switched on one by one
-// through attribution builds: docs/EXPERIMENTS.md) was also the default; ~2x the time of k_render_bwd_t.
-#define BSR_BWD_BATCH 128
-// Row stride of the per-wave partial sums: the 9 (10) storing lanes of one entry write part[wave][k][j] for
-// k = 0..NV-1 with ONE ds_write_b32 (bank = dword address mod 32, lanes of a 32-lane half conflict).  With rows of
-// 128 floats all of them hit one bank; 129 puts component k on bank (k + j) mod 32.
-#define BSR_BWD_ROW (BSR_BWD_BATCH + 1)
-template <int NV>
-struct BwdShared {
-	TileStageT<BSR_BWD_BATCH> st;
-	float part[4][NV][BSR_BWD_ROW];   // per-wave partial sums of the current batch (plain stores)
-	uint32_t max_contrib[4];
-};
-
-// State a pixel carries along the list (back to front) and the constants of the pixel.
-struct PairState {
-	float T;
-	float acc_rec[4], last_color[4], last_alpha;   // reference :527-536 channel by channel ([3] = depth, extension)
-};
-struct PixelConst {
-	float dpx0, dpx1, dpx2, neg_Tfinal_bg, gz, g1, ddelx_dx, ddely_dy;
-};
-// Per pair the reference adds (:574-583), with dL_dG = o * dL_dalpha:
-//   dL_dmean2D.x += dL_dG * dG_ddelx * ddelx_dx      dL_dconic.x += -0.5 gdx dx dL_dG
-//   dL_dmean2D.y += dL_dG * dG_ddely * ddely_dy      dL_dconic.y += -0.5 gdx dy dL_dG
-//   dL_dopacity  += G * dL_dalpha                    dL_dconic.w += -0.5 gdy dy dL_dG
-// (source order: this translation unit is built with -ffp-contract=off)
-template <bool DEPTH>
-__device__ __forceinline__ void pair_terms_reference(PairState& st, const PixelConst& px, const float4 q0, const float4 q1,
-                                                     const float4 q2, const float dx, const float dy, const float G,
-                                                     const float alpha, float (&v)[10])
-{
-	const float om = 1.f - alpha;
-	const float inv = 1.0f / om;
-	st.T = st.T / om;   // reference :521
-	const float T = st.T;
-	// accum_rec = last_alpha * last_color + (1 - last_alpha) * accum_rec, then (c - accum_rec) * dL_dpixel.  A pair the
-	// reference skips must leave (accum_rec, last_color, last_alpha) standing.  The depth extension is the oracle's
-	// separate pass (bsro_render_backward_depth): its own recurrence on d_i = gz z_i + g1.
-	const bool live = G != 0.f;
-	const float c4[4] = {q2.x, q2.y, q2.z, DEPTH ? px.gz * q1.w + px.g1 : 0.f};
-	const float dp[3] = {px.dpx0, px.dpx1, px.dpx2};
-	float S = 0.f, Sd = 0.f;
-#pragma unroll
-	for (int ch = 0; ch < (DEPTH ? 4 : 3); ch++) {
-		const float ar = st.last_alpha * st.last_color[ch] + (1.f - st.last_alpha) * st.acc_rec[ch];
-		st.acc_rec[ch] = live ? ar : st.acc_rec[ch];
-		st.last_color[ch] = live ? c4[ch] : st.last_color[ch];
-		if (ch < 3) S += (c4[ch] - st.acc_rec[ch]) * dp[ch];
-		else Sd = c4[ch] - st.acc_rec[ch];
-	}
-	st.last_alpha = live ? alpha : st.last_alpha;
-	const float dL_dalpha = T * S + px.neg_Tfinal_bg * inv;
-	const float ca = -2.0f * q0.z, cb = -q0.w, cc = -2.0f * q1.x;
-	const float gdx = G * dx, gdy = G * dy;
-	const float dG_ddelx = -gdx * ca - gdy * cb;
-	const float dG_ddely = -gdy * cc - gdx * cb;
-	float dL_dG = q1.z * dL_dalpha;
-	v[0] = dL_dG * dG_ddelx * px.ddelx_dx;
-	v[1] = dL_dG * dG_ddely * px.ddely_dy;
-	v[2] = -0.5f * gdx * dx * dL_dG;
-	v[3] = -0.5f * gdx * dy * dL_dG;
-	v[4] = -0.5f * gdy * dy * dL_dG;
-	v[5] = G * dL_dalpha;
-	if (DEPTH) {   // the oracle's second pass: the same terms for dL_dalpha = T * (d_i - Rd)
-		const float dLa = T * Sd;
-		dL_dG = q1.z * dLa;
-		v[0] += dL_dG * dG_ddelx * px.ddelx_dx;
-		v[1] += dL_dG * dG_ddely * px.ddely_dy;
-		v[2] += -0.5f * gdx * dx * dL_dG;
-		v[3] += -0.5f * gdx * dy * dL_dG;
-		v[4] += -0.5f * gdy * dy * dL_dG;
-		v[5] += G * dLa;
-	}
-	const float aT = alpha * T;
-	v[6] = aT * px.dpx0;
-	v[7] = aT * px.dpx1;
-	v[8] = aT * px.dpx2;
-	v[9] = DEPTH ? aT * px.gz : 0.f;
-}
-
-// DEPTH = false: the reference's backward (dL_depths ignored).  DEPTH = true: the opt-in extension
-// that also differentiates the normalised depth target (math in
-// oracle/bsr_oracle.c:bsro_render_backward_depth): a tenth partial sum dL/dz per instance and one more
-// term in dL/dalpha.  out_depth is the forward's depth image (its zeros are the acc <= 0.5 gate).
-template <bool DEPTH>
-__global__ void __launch_bounds__(BSR_BLOCK) k_render_bwd_strict(int n_tiles, int gx, int W, int H,
-                                                                 const uint2* __restrict__ tile_range,
-                                                                 const uint32_t* __restrict__ point_list,
-                                                                 const float4* __restrict__ rec,
-                                                                 const uint32_t* __restrict__ wg_base,
-                                                                 const float* __restrict__ bg_color,
-                                                                 const float* __restrict__ final_Ts,
-                                                                 const uint32_t* __restrict__ n_contrib,
-                                                                 const float* __restrict__ dL_dpixels,
-                                                                 const float* __restrict__ out_depth,   // DEPTH only
-                                                                 const float* __restrict__ dL_depths,   // DEPTH only
-                                                                 const int* __restrict__ masks_flag,    // forward's hand-over word (flags[6]; flags[2] = kept instances)
-                                                                 int capacity,                          // the R the call was handed
-                                                                 float4* __restrict__ slab)        // [R][9 or 10 floats]
-{
-	constexpr int NV = DEPTH ? 10 : 9;
-	__shared__ BwdShared<NV> sh;
-
-	const int tile = xcd_tile(blockIdx.x, n_tiles);
-	if (tile >= n_tiles) return;
-	// more instances kept than the R this call was handed: an overflowed BSR_FLAG_NO_READBACK forward -- no lists exist
-	// (k_preprocess_bwd writes NaN gradients, the thread's next forward reports it)
-	if (__builtin_amdgcn_readfirstlane(masks_flag[-4]) > capacity) return;
-	const int tid = threadIdx.x;
-	const int wave = tid >> 6, lane = tid & 63;
-	const int tx = tile % gx, ty = tile / gx;
-	const int px = tx * BSR_TILE + ((wave & 1) << 3) + (lane & 7);
-	const int py = ty * BSR_TILE + ((wave >> 1) << 3) + (lane >> 3);
-	const bool inside = px < W && py < H;
-	const float pixfx = (float)px, pixfy = (float)py;
-	const float tile_x0 = (float)(tx * BSR_TILE), tile_y0 = (float)(ty * BSR_TILE);
-	const size_t pix_id = (size_t)W * py + px;
-	const size_t plane = (size_t)H * W;
-
-	const uint2 range = tile_range[tile];
-	const uint32_t start = range.x;
-	const int n = (int)(range.y - range.x);
-	// (the forward may have left its box tests in the top byte of the point_list words: k_render_bwd_t; unused here)
-	const uint32_t id_mask = __builtin_amdgcn_readfirstlane(*masks_flag) != 0 ? 0x00ffffffu : 0xffffffffu;
-
-	const float T_final = inside ? final_Ts[pix_id] : 0.0f;
-	PairState pst = {};
-	pst.T = T_final;
-	const uint32_t last_contributor = inside ? n_contrib[pix_id] : 0u;
-	PixelConst pc = {};
-	if (inside) {
-		pc.dpx0 = dL_dpixels[pix_id];
-		pc.dpx1 = dL_dpixels[plane + pix_id];
-		pc.dpx2 = dL_dpixels[2 * plane + pix_id];
-	}
-	const float bg_dot_dpixel = bg_color[0] * pc.dpx0 + bg_color[1] * pc.dpx1 + bg_color[2] * pc.dpx2;
-	pc.neg_Tfinal_bg = -T_final * bg_dot_dpixel;
-	// depth extension: d_i = gz * z_i + g1 plays the role of a fourth colour channel
-	if (DEPTH && inside) {
-		const float depth_px = out_depth[pix_id];
-		if (depth_px != 0.0f) {   // the forward's acc > 0.5 decision
-			pc.gz = dL_depths[pix_id] / (1e-6f + (1.0f - T_final));
-			pc.g1 = -pc.gz * depth_px;
-		}
-	}
-	// component whose wave total lands in this lane after the reduction; one lane per component stores
-	bool stores;
-	const int comp_of_lane = calibrate_components<DEPTH>(lane, stores);
-	float* const part_mine = &sh.part[wave][stores ? comp_of_lane : 0][0];
-	pc.ddelx_dx = (float)(0.5 * W);
-	pc.ddely_dy = (float)(0.5 * H);
-
-	// Entries at list positions >= max(last_contributor) are skipped by every pixel of the tile
-	// (reference :498-500): start the walk at the deepest entry any pixel blended.
-	uint32_t m = last_contributor;
-#pragma unroll
-	for (int d = 32; d > 0; d >>= 1) m = max(m, (uint32_t)__shfl_xor((int)m, d, 64));
-	if (lane == 0) sh.max_contrib[wave] = m;
-	if (tid < BSR_BWD_BATCH) {
-#pragma unroll
-		for (int w = 0; w < 4; w++)
-#pragma unroll
-			for (int k = 0; k < NV; k++) sh.part[w][k][tid] = 0.f;
-	}
-	__syncthreads();
-	const int n_walk = (int)max(max(sh.max_contrib[0], sh.max_contrib[1]), max(sh.max_contrib[2], sh.max_contrib[3]));
-
-	for (int base = 0; base < n_walk; base += BSR_BWD_BATCH) {
-		const int cnt = min(BSR_BWD_BATCH, n_walk - base);
-		const int top = n_walk - 1 - base;   // list position of batch entry j is top - j
-		const bool valid = tid < cnt;
-		uint32_t my_row = 0;
-		float4 r0 = make_float4(0.f, 0.f, 0.f, 0.f), r1 = r0, r2 = r0;
-		if (valid) {
-			const uint32_t my_slot = start + (uint32_t)(top - tid);
-			const uint32_t id = point_list[my_slot] & id_mask;
-			const float4* r = rec + (size_t)id * BSR_REC;   // one 64-B line: record + rect + instance offset
-			r0 = r[0];
-			r1 = r[1];
-			r2 = r[2];
-			my_row = instance_index(wg_base, id, r2, r[3], tx, ty);   // the entry's row in the Gaussian-major slab
-		}
-		// (the trailing barrier of the previous iteration fenced the staging buffers)
-		const int n_mine = stage_and_compact(sh.st, tid, valid, r0, r1, r2, tile_x0, tile_y0);
-		const int n_u = __builtin_amdgcn_readfirstlane(n_mine);
-		// entry j of the batch sits at list position top - j; this pixel blended positions < last_contributor
-		// (reference :498-500): j > top - last_contributor, compared on the pre-scaled list offsets
-		const int joff_min = (top - (int)last_contributor) * 16;
-		auto visit = [&](const unsigned int joff) {
-			const char* rec = stage_rec(sh.st, joff);
-			const float4 q0 = rec_q0<BSR_BWD_BATCH>(rec);
-			const float4 q1 = rec_q1<BSR_BWD_BATCH>(rec);   // conic c, power cut, opacity, depth
-			const float dx = q0.x - pixfx;
-			const float dy = q0.y - pixfy;
-			const float power = (q0.z * dx * dx + q1.x * dy * dy) + q0.w * dx * dy;   // pre-scaled conic (common.h): the forward's bits
-			const bool cand = ((int)joff > joff_min) && !(power > 0.0f) && !(power < q1.y);
-			if (wave_ballot(cand) == 0ull) return;   // wave-uniform
-			const float4 q2 = rec_q2<BSR_BWD_BATCH>(rec);
-			// The forward decided `alpha >= 1/255` on alpha = min(0.99, o * E(power)) with the pinned exp E (bsr_expf) --
-			// in its default mode only inside the decision band, outside of which every exp within ulps decides alike
-			// (render_fwd.hip) -- and the backward must take the same decision on every pair (the T chain divides by the
-			// same factors the forward multiplied).  Lanes that must not blend carry G = 0, hence alpha = 0: every
-			// recurrence then leaves their state unchanged (T / 1 = T) and all nine contributions are exactly 0.
-			float G = cand ? bsr_expf_walk(power) : 0.f;
-			float alpha = fminf(0.99f, q1.z * G);
-			const bool active = !(alpha < 1.0f / 255.0f);
-			if (wave_ballot(active) == 0ull) return;
-			G = active ? G : 0.f;
-			alpha = active ? alpha : 0.f;
-			float v[10];
-			pair_terms_reference<DEPTH>(pst, pc, q0, q1, q2, dx, dy, G, alpha, v);
-			const float tot = wave_sums_masked<DEPTH>(v[0], v[1], v[2], v[3], v[4], v[5], v[6], v[7], v[8], v[9]);
-			if (stores) *reinterpret_cast<float*>(reinterpret_cast<char*>(part_mine) + (joff >> 2)) = tot;   // part_mine[j]
-		};
-		// four list entries per trip: one address computation and one 16-byte LDS read for the list
-		for (int i = 0; i < n_u; i += 4) {
-			const uint4 l = *reinterpret_cast<const uint4*>(&sh.st.list[wave][i]);   // (reads past the end stay inside the list)
-			visit(l.x);
-			if (i + 1 < n_u) visit(l.y);
-			if (i + 2 < n_u) visit(l.z);
-			if (i + 3 < n_u) visit(l.w);
-		}
-		__syncthreads();
-		if (valid) {
-			float a9[10];
-			a9[9] = 0.f;
-#pragma unroll
-			for (int k = 0; k < NV; k++) {   // fixed order over the 4 quadrants -> deterministic
-				a9[k] = ((sh.part[0][k][tid] + sh.part[1][k][tid]) + sh.part[2][k][tid]) + sh.part[3][k][tid];
-				sh.part[0][k][tid] = 0.f;
-				sh.part[1][k][tid] = 0.f;
-				sh.part[2][k][tid] = 0.f;
-				sh.part[3][k][tid] = 0.f;
-			}
-			float* const row = reinterpret_cast<float*>(slab) + (size_t)my_row * slab_row_floats(DEPTH);
-			*reinterpret_cast<bsr_f32x4_a4*>(row) = bsr_f32x4{a9[0], a9[1], a9[2], a9[3]};
-			*reinterpret_cast<bsr_f32x4_a4*>(row + 4) = bsr_f32x4{a9[4], a9[5], a9[6], a9[7]};
-			if (DEPTH) *reinterpret_cast<bsr_f32x2_a4*>(row + 8) = bsr_f32x2{a9[8], a9[9]};
-			else row[8] = a9[8];
-		}
-		__syncthreads();
-	}
-
-	// entries no pixel of the tile reached: zero rows, but they still need their map entry
-	for (int pos = n_walk + tid; pos < n; pos += BSR_BLOCK) {
-		const uint32_t slot = start + (uint32_t)pos;
-		const uint32_t id = point_list[slot] & id_mask;
-		float* const row = reinterpret_cast<float*>(slab) +
-		                   (size_t)instance_index(wg_base, id, rec[(size_t)id * BSR_REC + 2], rec[(size_t)id * BSR_REC + 3],
-		                                          tx, ty) * slab_row_floats(DEPTH);
-		const bsr_f32x4 z = {0.f, 0.f, 0.f, 0.f};
-		*reinterpret_cast<bsr_f32x4_a4*>(row) = z;
-		*reinterpret_cast<bsr_f32x4_a4*>(row + 4) = z;
-		if (DEPTH) *reinterpret_cast<bsr_f32x2_a4*>(row + 8) = bsr_f32x2{0.f, 0.f};
-		else row[8] = 0.f;
-	}
-}
-
-// =====================================================================================================================
 // k_render_bwd_t: the default backward walk.  Per-pixel decisions as the reference; the cross-lane reduction of the
 // entry's nine (ten) sums is TRANSPOSED through LDS and runs at full lane utilisation:
 //
@@ -440,6 +39,12 @@ __global__ void __launch_bounds__(BSR_BLOCK) k_render_bwd_strict(int n_tiles, in
 // (scalar-cache records, LDS atomics, sums filed by list position, pair-padded lists, blocks of four entries, shared
 // staging, a trailing barrier, list words prefetched a batch ahead, ...): docs/EXPERIMENTS.md.
 // The depth-gradient instantiation (ten sums per entry) keeps NS = 1: with split lists it spills.
+#include "bwd_sums.h"
+#include "render_bwd_common.h"
+#include "launch.h"
+
+namespace bsr {
+
 #ifndef BSR_BWT_BATCH
 #define BSR_BWT_BATCH 64
 #endif
@@ -462,93 +67,6 @@ struct BwtShared {
 	uint32_t max_contrib[4];
 	alignas(16) char tbuf[4][BSR_BWT_CHUNK * BSR_BWT_SLOT];   // per wave: [slot][row][col] x (gd, aT)
 };
-
-// Sum over the 8 lanes sharing (lane >> 3) of nine (ten) values.  On return, in every lane with bit 2 clear x0..x3 (x4
-// with TEN) hold the totals of inputs 0..3 (0..4) and x8 that of input 8; in lanes with bit 2 set x0..x3 (x4) hold the
-// totals of inputs 4..7 (5..9).  Step over lane bit 2 = halving on bank-masked row rotations (rotate by 12 = "from
-// lane + 4" into banks 0 and 2, rotate by 4 = "from lane - 4" into banks 1 and 3: both stay inside the 8-lane group), steps
-// over bits 1 and 0 = plain quad permutes.  19 (20) instructions.  Inline asm gets no automatic wait states: a DPP read
-// needs 2 after a VALU write of the same VGPR -- the order keeps >= 2 instructions between, s_nop at the start.
-template <bool TEN>
-__device__ __forceinline__ void row8_sums(float& x0, float& x1, float& x2, float& x3, float& x4, float& x5, float& x6,
-                                          float& x7, float& x8, float& x9)
-{
-	if (TEN) {
-		asm volatile(
-		    "s_nop 1\n"
-		    "v_add_f32_dpp %0, %0, %0 row_ror:12 row_mask:0xf bank_mask:0x5\n"
-		    "v_add_f32_dpp %1, %1, %1 row_ror:12 row_mask:0xf bank_mask:0x5\n"
-		    "v_add_f32_dpp %2, %2, %2 row_ror:12 row_mask:0xf bank_mask:0x5\n"
-		    "v_add_f32_dpp %3, %3, %3 row_ror:12 row_mask:0xf bank_mask:0x5\n"
-		    "v_add_f32_dpp %4, %4, %4 row_ror:12 row_mask:0xf bank_mask:0x5\n"
-		    "v_add_f32_dpp %0, %5, %5 row_ror:4 row_mask:0xf bank_mask:0xa\n"
-		    "v_add_f32_dpp %1, %6, %6 row_ror:4 row_mask:0xf bank_mask:0xa\n"
-		    "v_add_f32_dpp %2, %7, %7 row_ror:4 row_mask:0xf bank_mask:0xa\n"
-		    "v_add_f32_dpp %3, %8, %8 row_ror:4 row_mask:0xf bank_mask:0xa\n"
-		    "v_add_f32_dpp %4, %9, %9 row_ror:4 row_mask:0xf bank_mask:0xa\n"
-		    "v_add_f32_dpp %0, %0, %0 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n"
-		    "v_add_f32_dpp %1, %1, %1 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n"
-		    "v_add_f32_dpp %2, %2, %2 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n"
-		    "v_add_f32_dpp %3, %3, %3 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n"
-		    "v_add_f32_dpp %4, %4, %4 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n"
-		    "v_add_f32_dpp %0, %0, %0 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n"
-		    "v_add_f32_dpp %1, %1, %1 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n"
-		    "v_add_f32_dpp %2, %2, %2 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n"
-		    "v_add_f32_dpp %3, %3, %3 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n"
-		    "v_add_f32_dpp %4, %4, %4 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n"
-		    : "+v"(x0), "+v"(x1), "+v"(x2), "+v"(x3), "+v"(x4), "+v"(x5), "+v"(x6), "+v"(x7), "+v"(x8), "+v"(x9));
-	} else {
-		asm volatile(
-		    "s_nop 1\n"
-		    "v_add_f32_dpp %0, %0, %0 row_ror:12 row_mask:0xf bank_mask:0x5\n"
-		    "v_add_f32_dpp %1, %1, %1 row_ror:12 row_mask:0xf bank_mask:0x5\n"
-		    "v_add_f32_dpp %2, %2, %2 row_ror:12 row_mask:0xf bank_mask:0x5\n"
-		    "v_add_f32_dpp %3, %3, %3 row_ror:12 row_mask:0xf bank_mask:0x5\n"
-		    "v_add_f32_dpp %8, %8, %8 row_ror:12 row_mask:0xf bank_mask:0x5\n"
-		    "v_add_f32_dpp %0, %4, %4 row_ror:4 row_mask:0xf bank_mask:0xa\n"
-		    "v_add_f32_dpp %1, %5, %5 row_ror:4 row_mask:0xf bank_mask:0xa\n"
-		    "v_add_f32_dpp %2, %6, %6 row_ror:4 row_mask:0xf bank_mask:0xa\n"
-		    "v_add_f32_dpp %3, %7, %7 row_ror:4 row_mask:0xf bank_mask:0xa\n"
-		    "v_add_f32_dpp %0, %0, %0 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n"
-		    "v_add_f32_dpp %1, %1, %1 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n"
-		    "v_add_f32_dpp %2, %2, %2 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n"
-		    "v_add_f32_dpp %3, %3, %3 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n"
-		    "v_add_f32_dpp %8, %8, %8 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n"
-		    "v_add_f32_dpp %0, %0, %0 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n"
-		    "v_add_f32_dpp %1, %1, %1 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n"
-		    "v_add_f32_dpp %2, %2, %2 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n"
-		    "v_add_f32_dpp %3, %3, %3 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n"
-		    "v_add_f32_dpp %8, %8, %8 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n"
-		    : "+v"(x0), "+v"(x1), "+v"(x2), "+v"(x3), "+v"(x4), "+v"(x5), "+v"(x6), "+v"(x7), "+v"(x8), "+v"(x9));
-	}
-}
-
-// NS = 2: the 8 lanes of a slot hold TWO entries (rows 0-3 | rows 4-7): the sums stop at the quad.  On return every
-// lane holds the totals of its quad (its half of the slot) in all nine (ten) registers.  18 (20) instructions.
-template <bool TEN>
-__device__ __forceinline__ void row4_sums(float& x0, float& x1, float& x2, float& x3, float& x4, float& x5, float& x6,
-                                          float& x7, float& x8, float& x9)
-{
-#define BSR_QSTEP(P)                                                                   \
-	"v_add_f32_dpp %0, %0, %0 quad_perm:" P " row_mask:0xf bank_mask:0xf\n"           \
-	"v_add_f32_dpp %1, %1, %1 quad_perm:" P " row_mask:0xf bank_mask:0xf\n"           \
-	"v_add_f32_dpp %2, %2, %2 quad_perm:" P " row_mask:0xf bank_mask:0xf\n"           \
-	"v_add_f32_dpp %3, %3, %3 quad_perm:" P " row_mask:0xf bank_mask:0xf\n"           \
-	"v_add_f32_dpp %4, %4, %4 quad_perm:" P " row_mask:0xf bank_mask:0xf\n"           \
-	"v_add_f32_dpp %5, %5, %5 quad_perm:" P " row_mask:0xf bank_mask:0xf\n"           \
-	"v_add_f32_dpp %6, %6, %6 quad_perm:" P " row_mask:0xf bank_mask:0xf\n"           \
-	"v_add_f32_dpp %7, %7, %7 quad_perm:" P " row_mask:0xf bank_mask:0xf\n"           \
-	"v_add_f32_dpp %8, %8, %8 quad_perm:" P " row_mask:0xf bank_mask:0xf\n"
-	if (TEN) {
-		asm volatile("s_nop 1\n" BSR_QSTEP("[2,3,0,1]") "v_add_f32_dpp %9, %9, %9 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n"
-		             BSR_QSTEP("[1,0,3,2]") "v_add_f32_dpp %9, %9, %9 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n"
-		             : "+v"(x0), "+v"(x1), "+v"(x2), "+v"(x3), "+v"(x4), "+v"(x5), "+v"(x6), "+v"(x7), "+v"(x8), "+v"(x9));
-	} else {
-		asm volatile("s_nop 1\n" BSR_QSTEP("[2,3,0,1]") BSR_QSTEP("[1,0,3,2]")
-		             : "+v"(x0), "+v"(x1), "+v"(x2), "+v"(x3), "+v"(x4), "+v"(x5), "+v"(x6), "+v"(x7), "+v"(x8), "+v"(x9));
-	}
-#undef BSR_QSTEP
-}
 
 #ifdef BSR_WALK_TIMELINE
 // (make timeline: per-workgroup start / end stamps of the default backward walk; tools/walk_stats.py --timeline)
@@ -593,6 +111,7 @@ __global__ void __launch_bounds__(BSR_BLOCK) BSR_BWT_WAVES_ATTR k_render_bwd_t(i
 #ifdef BSR_WALK_TIMELINE
 	const unsigned long long t_start = __builtin_amdgcn_s_memrealtime();
 #endif
+	// (the per-pixel prologue, down to ddely_dy, is written out in both walks: render_bwd_common.h)
 	const int tid = threadIdx.x;
 	const int wave = tid >> 6, lane = tid & 63;
 	const int tx = tile % gx, ty = tile / gx;
@@ -671,6 +190,7 @@ __global__ void __launch_bounds__(BSR_BLOCK) BSR_BWT_WAVES_ATTR k_render_bwd_t(i
 
 	// Entries at list positions >= max(last_contributor) are skipped by every pixel of the tile
 	// (reference :498-500): start the walk at the deepest entry any pixel blended.
+	// (written out in both walks: render_bwd_common.h)
 	uint32_t m = last_contributor;
 #pragma unroll
 	for (int d = 32; d > 0; d >>= 1) m = max(m, (uint32_t)__shfl_xor((int)m, d, 64));
@@ -761,7 +281,7 @@ __global__ void __launch_bounds__(BSR_BLOCK) BSR_BWT_WAVES_ATTR k_render_bwd_t(i
 		// entries' LDS reads and their power / exp / alpha chains are independent and the scheduler interleaves them; only
 		// T and Srec are serial.  No vote per entry, no early return: a lane that must not blend carries G = 0, hence
 		// alpha = 0, which leaves its state unchanged (T / 1 = T, Srec + 0 S = Srec) and stores gd = aT = 0; the rows are
-		// sentinel-padded to whole chunks and a sentinel is never a candidate.  Decisions exactly as k_render_bwd: the
+		// sentinel-padded to whole chunks and a sentinel is never a candidate.  Decisions exactly as k_render_bwd_strict: the
 		// forward decided `alpha >= 1/255` with the pinned exp; only a trip holding a candidate lane inside the decision
 		// band (q2.w = its upper edge) evaluates the pinned exp and tests alpha, everywhere else the value comes from
 		// v_exp_f32.  (Testing alpha on a trip's other entries changes nothing: outside the band every candidate has
@@ -790,7 +310,7 @@ __global__ void __launch_bounds__(BSR_BLOCK) BSR_BWT_WAVES_ATTR k_render_bwd_t(i
 				const float om = 1.f - alpha;
 				const float inv = __builtin_amdgcn_rcpf(om);   // 1 ulp
 				const float qT = T * inv;
-				T = __builtin_fmaf(__builtin_fmaf(-om, qT, T), inv, qT);   // T / (1 - alpha), residual-corrected (see k_render_bwd)
+				T = __builtin_fmaf(__builtin_fmaf(-om, qT, T), inv, qT);   // T / (1 - alpha), residual-corrected (k_render_bwd_strict divides)
 				float u = e.q2.x * dpx0 + e.q2.y * dpx1 + e.q2.z * dpx2;
 				if (DEPTH) u += __builtin_fmaf(gz, e.q1.w, g1);
 				const float S = u - Srec;
@@ -944,24 +464,16 @@ __global__ void __launch_bounds__(BSR_BLOCK) BSR_BWT_WAVES_ATTR k_render_bwd_t(i
 			float a9[10];
 			a9[9] = 0.f;
 #pragma unroll
-			for (int k = 0; k < NV; k++) {   // fixed order over the 4 quadrants -> deterministic
-				a9[k] = ((sh.part[0][k][tid] + sh.part[1][k][tid]) + sh.part[2][k][tid]) + sh.part[3][k][tid];
-				sh.part[0][k][tid] = 0.f;
-				sh.part[1][k][tid] = 0.f;
-				sh.part[2][k][tid] = 0.f;
-				sh.part[3][k][tid] = 0.f;
-			}
-			// the wave sums -> the reference's sums (see k_render_bwd); this thread staged entry `tid` itself
+			for (int k = 0; k < NV; k++) a9[k] = take_quadrant_sum(sh.part, k, tid);
+			// the wave sums -> the reference's sums (pair_terms_reference, render_bwd_strict.hip); this thread staged entry `tid` itself
 			const float4 e0 = sh.st.q0[tid], e1 = sh.st.q1[tid];   // (x, y, -a/2, -b), (-c/2, cut, o, depth)
 			const float ca = -2.0f * e0.z, cb = -e0.w, cc = -2.0f * e1.x;
 			const float no = -e1.z;
 			const float h = 0.5f * no;
 			float* const row = reinterpret_cast<float*>(slab) + (size_t)my_row * slab_row_floats(DEPTH);
-			*reinterpret_cast<bsr_f32x4_a4*>(row) = bsr_f32x4{no * ddelx_dx * (ca * a9[0] + cb * a9[1]),
-			                                                   no * ddely_dy * (cc * a9[1] + cb * a9[0]), h * a9[2], h * a9[3]};
-			*reinterpret_cast<bsr_f32x4_a4*>(row + 4) = bsr_f32x4{h * a9[4], a9[5], a9[6], a9[7]};
-			if (DEPTH) *reinterpret_cast<bsr_f32x2_a4*>(row + 8) = bsr_f32x2{a9[8], a9[9]};
-			else row[8] = a9[8];
+			const float v[10] = {no * ddelx_dx * (ca * a9[0] + cb * a9[1]), no * ddely_dy * (cc * a9[1] + cb * a9[0]), h * a9[2], h * a9[3],
+			                     h * a9[4], a9[5], a9[6], a9[7], a9[8], a9[9]};
+			store_slab_row<DEPTH>(row, v);
 		}
 		// No barrier here: while wave 0 adds up the batch, waves 1-3 already stage the next one.  Safe ONLY while all of
 		// these hold:  (1) only wave 0 writes st.q0 / q1 / q2 and reads or zeroes part[][];  (2) a wave's lists and its
@@ -974,19 +486,7 @@ __global__ void __launch_bounds__(BSR_BLOCK) BSR_BWT_WAVES_ATTR k_render_bwd_t(i
 #endif
 	}
 
-	// entries no pixel of the tile reached: zero rows, but they still need their map entry
-	for (int pos = n_walk + tid; pos < n; pos += BSR_BLOCK) {
-		const uint32_t slot = start + (uint32_t)pos;
-		const uint32_t id = point_list[slot] & id_mask;
-		float* const row = reinterpret_cast<float*>(slab) +
-		                   (size_t)instance_index(wg_base, id, rec[(size_t)id * BSR_REC + 2], rec[(size_t)id * BSR_REC + 3],
-		                                          tx, ty) * slab_row_floats(DEPTH);
-		const bsr_f32x4 z = {0.f, 0.f, 0.f, 0.f};
-		*reinterpret_cast<bsr_f32x4_a4*>(row) = z;
-		*reinterpret_cast<bsr_f32x4_a4*>(row + 4) = z;
-		if (DEPTH) *reinterpret_cast<bsr_f32x2_a4*>(row + 8) = bsr_f32x2{0.f, 0.f};
-		else row[8] = 0.f;
-	}
+	zero_unreached_rows<DEPTH>(n_walk, n, tid, start, point_list, id_mask, rec, wg_base, tx, ty, slab);
 #ifdef BSR_WALK_TIMELINE
 	if (tid == 0 && tile < 70000) {   // (wave 0 leaves last or nearly so: it owns every batch's epilogue; filed under the tile)
 		unsigned long long* t = g_bwd_times + 4 * (size_t)tile;
@@ -1001,40 +501,27 @@ __global__ void __launch_bounds__(BSR_BLOCK) BSR_BWT_WAVES_ATTR k_render_bwd_t(i
 #endif
 }
 
-void launch_render_bwd(int gx, int gy, int W, int H, const uint2* tile_range, const uint32_t* point_list,
-                       const float4* rec, const uint32_t* wg_base, const float* bg, const float* final_T,
-                       const uint32_t* n_contrib, const float* dL_dpix, const float* out_depth, const float* dL_depths,
-                       int* masks_flag, float4* slab, bool strict, int num_rendered, hipStream_t s)
+template <bool DEPTH, int NS>
+static void launch_bwt(const RenderBwdArgs& a, hipStream_t s)
 {
-	const int n_tiles = gx * gy;
-	const int blocks = ((n_tiles + 7) / 8) * 8;
-	const unsigned pad = occupancy_sweep_lds_pad("BSR_SWEEP_LDS_PAD_BWD");
-	const bool depth = out_depth && dL_depths;
-#define BSR_LAUNCH_STRICT(D_)                                                                                            \
-	hipLaunchKernelGGL((k_render_bwd_strict<D_>), dim3(blocks), dim3(BSR_BLOCK), pad, s, n_tiles, gx, W, H, tile_range,     \
-	                   point_list, rec, wg_base, bg, final_T, n_contrib, dL_dpix, depth ? out_depth : nullptr,           \
-	                   depth ? dL_depths : nullptr, masks_flag, num_rendered, slab)
-#define BSR_LAUNCH_BWT(D_, N_)                                                                                             \
-	hipLaunchKernelGGL((k_render_bwd_t<D_, N_>), dim3(pooled_grid(n_tiles)), dim3(BSR_BLOCK), pad, s, n_tiles, gx, W, H,      \
-	                   tile_range, point_list, rec, wg_base, bg, final_T, n_contrib, dL_dpix, depth ? out_depth : nullptr,   \
-	                   depth ? dL_depths : nullptr, masks_flag, num_rendered, slab)
-	// Default: the transposed-reduction walk, for every frame.  (Until round 5 frames with > 1900 reference instances
-	// per tile -- C5, scales x 3 -- kept round 3's per-visit network walk, 0-4 % faster there; with the forward's half
-	// masks handed over, k_render_bwd_t is 5 % faster at C5 and within 1.5 % on the dense scene: docs/EXPERIMENTS.md.)
-	// BSR_FLAG_EXACT_GRAD: k_render_bwd_strict.
-	if (strict) {
-		if (depth) BSR_LAUNCH_STRICT(true);
-		else BSR_LAUNCH_STRICT(false);
-	} else if (depth) {
+	const int n_tiles = a.gx * a.gy;
+	hipLaunchKernelGGL((k_render_bwd_t<DEPTH, NS>), dim3(pooled_grid(n_tiles)), dim3(BSR_BLOCK), occupancy_sweep_lds_pad("BSR_SWEEP_LDS_PAD_BWD"),
+	                   s, n_tiles, a.gx, a.W, a.H, a.tile_range, a.point_list, a.rec, a.wg_base, a.bg, a.final_T, a.n_contrib,
+	                   a.dL_dpix, DEPTH ? a.out_depth : nullptr, DEPTH ? a.dL_depths : nullptr, a.masks_flag, a.capacity, a.slab);
+}
+
+// Default: the transposed-reduction walk, for every frame.  (Until round 5 frames with > 1900 reference instances
+// per tile -- C5, scales x 3 -- kept round 3's per-visit network walk, 0-4 % faster there; with the forward's half
+// masks handed over, k_render_bwd_t is 5 % faster at C5 and within 1.5 % on the dense scene: docs/EXPERIMENTS.md.)
+// BSR_FLAG_EXACT_GRAD: k_render_bwd_strict.
+void launch_render_bwd(const RenderBwdArgs& a, hipStream_t s)
+{
 #ifndef BSR_BWT_DEPTH_NS
 #define BSR_BWT_DEPTH_NS 1
 #endif
-		BSR_LAUNCH_BWT(true, BSR_BWT_DEPTH_NS);    // (ten sums per entry: with split lists the kernel spills and loses 8 %)
-	} else {
-		BSR_LAUNCH_BWT(false, 2);
-	}
-#undef BSR_LAUNCH_STRICT
-#undef BSR_LAUNCH_BWT
+	if (a.strict) launch_render_bwd_strict(a, s);
+	else if (a.out_depth && a.dL_depths) launch_bwt<true, BSR_BWT_DEPTH_NS>(a, s);   // (ten sums per entry: with split lists the kernel spills and loses 8 %)
+	else launch_bwt<false, 2>(a, s);
 }
 
 }  // namespace bsr

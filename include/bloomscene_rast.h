@@ -46,7 +46,7 @@ extern "C" {
  *                      :433-437 sees a T that differs by those ulps.  Set: the pinned exp on every evaluation -- the
  *                      forward then matches the CPU oracle bit for bit.  Accepted and ignored by the backward (a caller
  *                      may hand one flags word to both).
- * BSR_FLAG_EXACT_GRAD  backward: 0 (default) = k_render_bwd evaluates each (pixel, Gaussian) pair with hardware exp
+ * BSR_FLAG_EXACT_GRAD  backward: 0 (default) = k_render_bwd_t evaluates each (pixel, Gaussian) pair with hardware exp
  *                      outside the decision band, reciprocal + one refinement instead of the two divisions, fused
  *                      multiply-adds, moment sums and one projected accum_rec (DESIGN.md "Numerics").  Set: the reference's
  *                      per-pair operations on the reference's operands (backward.cu:521,527-536,557,561-583: IEEE

@@ -242,7 +242,7 @@ def contracted_oracle_grads(c):
 
 
 def assert_strict_gradient_parity(c, st, g, grads, label="", keys=GRAD_KEYS):
-    """Gradients of a BSR_FLAG_EXACT_GRAD (strict_gradients=True) call against the oracle: k_render_bwd then performs
+    """Gradients of a BSR_FLAG_EXACT_GRAD (strict_gradients=True) call against the oracle: k_render_bwd_strict then performs
     the reference's per-pair operations on the reference's operands (backward.cu:521,527-536,557,561-583) and only the
     ORDER of the nine sums differs, so SURVEY.md 8(d)'s share of elements beyond 1e-4 relative must not exceed what
     summation order alone costs the reference -- the oracle's fp32 terms added in binary32 in one fixed order against
@@ -303,7 +303,7 @@ def assert_gradient_parity(c, st, g, grads, label="", keys=GRAD_KEYS, report=Non
         gives per-pair terms that differ by an ulp here and there, and the f64 sums of the two then differ by more
         than 1e-4 on a 4e-4 .. 2e-3 share (contracted_oracle_grads).  Any implementation whose per-pair arithmetic is
         not operation-for-operation the oracle's lands there too: round 3's attribution builds show every
-        single shortcut of k_render_bwd switched off alone changing the share by < 15 %, all of them off together
+        single shortcut of the backward walk switched off alone changing the share by < 15 %, all of them off together
         bringing it to 0.5x the summation floor.
     The larger of the two measured shares is the floor of any elementwise comparison, so the assertions are
       scale < 1e-5                                  (every tensor, every case; observed <= 6e-6)

@@ -2,9 +2,11 @@
 // that the python restatements of tests/test_box_test_cpu.py, test_tile_pool_cpu.py, test_bin_elem_cpu.py and
 // test_scratch_layout_cpu.py are checked
 // against the code the kernels execute (an edit to box_may_hit, pooled_tile or the element packing would
-// otherwise leave those CPU tests green).  Built by tests/native/Makefile into libbsr_pure_functions.so; driven by
-// tests/test_round6_gpu.py through ctypes.  Nothing here is part of the product library.
+// otherwise leave those CPU tests green).  Also the backward walks' cross-lane sum networks (bwd_sums.h) on given
+// per-lane inputs, for tests/test_bwd_sums_gpu.py.  Built by tests/native/Makefile into libbsr_pure_functions.so; driven by
+// tests/test_round6_gpu.py and tests/test_bwd_sums_gpu.py through ctypes.  Nothing here is part of the product library.
 #include "../../bloomscene_amd/csrc/tile_common.h"
+#include "../../bloomscene_amd/csrc/bwd_sums.h"
 #include "../../bloomscene_amd/csrc/scratch.h"
 
 using namespace bsr;
@@ -47,7 +49,40 @@ __global__ void __launch_bounds__(256) k_pool(int n_tiles, int* pool_ctr, int* _
 	if (threadIdx.x == 0) tile_of_wg[blockIdx.x] = t;
 }
 
+// One wave runs one of bwd_sums.h's networks on in[v][lane] (10 x 64 floats).  network 0: wave_sums_masked ->
+// out[0][lane] = the value the lane ends with, aux[lane] = calibrate_components' component of the lane,
+// aux[64 + lane] = whether the lane stores it.  network 1: row8_sums, 2: row4_sums -> out[v][lane] = register v of the lane.
+template <bool TEN>
+__global__ void __launch_bounds__(64) k_bwd_sums(int network, const float* __restrict__ in, float* __restrict__ out,
+                                                 int* __restrict__ aux)
+{
+	const int lane = threadIdx.x;
+	float x[10];
+#pragma unroll
+	for (int v = 0; v < 10; v++) x[v] = in[v * 64 + lane];
+	if (network == 0) {
+		bool stores;
+		aux[lane] = calibrate_components<TEN>(lane, stores);
+		aux[64 + lane] = stores ? 1 : 0;
+		out[lane] = wave_sums_masked<TEN>(x[0], x[1], x[2], x[3], x[4], x[5], x[6], x[7], x[8], x[9]);
+		return;
+	}
+	if (network == 1) row8_sums<TEN>(x[0], x[1], x[2], x[3], x[4], x[5], x[6], x[7], x[8], x[9]);
+	else row4_sums<TEN>(x[0], x[1], x[2], x[3], x[4], x[5], x[6], x[7], x[8], x[9]);
+#pragma unroll
+	for (int v = 0; v < 10; v++) out[v * 64 + lane] = x[v];
+}
+
 extern "C" {
+
+// in, out: 10 x 64 floats; aux: 2 x 64 ints (network 0 only)
+int pt_bwd_sums(int network, int ten, const float* in, float* out, int* aux, void* stream)
+{
+	if (network < 0 || network > 2) return 1;
+	if (ten) hipLaunchKernelGGL((k_bwd_sums<true>), dim3(1), dim3(64), 0, (hipStream_t)stream, network, in, out, aux);
+	else hipLaunchKernelGGL((k_bwd_sums<false>), dim3(1), dim3(64), 0, (hipStream_t)stream, network, in, out, aux);
+	return hipGetLastError() == hipSuccess ? 0 : 2;
+}
 
 int pt_box_may_hit(int ext, int exty, int n, const float* X, const float* Y, const float* a, const float* b, const float* c,
                    const float* cut, const float* bx, const float* by, unsigned char* out, void* stream)

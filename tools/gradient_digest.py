@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """sha256 of every output of forward + backward on a few seeded scenes, for comparing two BUILDS of the library bit for bit:
-    python tools/gradient_digest.py [--lib other_build.so]   ->  one JSON line {case: {tensor: digest}}"""
+    python tools/gradient_digest.py [--lib other_build.so] [--strict | --pooled | --plans]   ->  one JSON line {case: {tensor: digest}}
+--strict: the same cases with strict_gradients=True (BSR_FLAG_EXACT_GRAD: k_render_bwd_strict instead of k_render_bwd_t)."""
 import hashlib, json, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -8,6 +9,7 @@ from bloomscene_amd import _capi
 if len(sys.argv) > 2 and sys.argv[1] == "--lib":
     _capi.use_library(sys.argv[2])
 import helpers as Hh
+STRICT = "--strict" in sys.argv
 POOLED = "--pooled" in sys.argv   # only the frame large enough for the tile walks' tail pool (>= 4096 tiles), twice
 
 CASES = {"c3_small": dict(P=60000, W=480, H=270, deg=3, seed=0), "dense": dict(P=40000, W=160, H=96, deg=1, seed=4, scale_mul=6.0),
@@ -43,7 +45,7 @@ for name, kw in CASES.items():
         zm = float(c.means3D[:, 2].median())
         c.means3D[:, 2] = torch.linspace(0.8 * zm, 1.2 * zm, z_levels)[torch.arange(c.P) % z_levels]
     for dg in ((False,) if "--plans" in sys.argv else (False, True)):
-        r = Hh.run_hip(c, depth_gradient=dg)
+        r = Hh.run_hip(c, depth_gradient=dg, strict_gradients=True if STRICT else None)
         d = {"color": r.color, "depth": r.depth, "radii": r.radii}
         d.update({"grad_" + k: getattr(r.grads, k) for k in Hh.GRAD_KEYS if getattr(r.grads, k) is not None})
         out[name + ("+depth" if dg else "")] = {k: hashlib.sha256(v.tobytes()).hexdigest()[:16] for k, v in d.items()}

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Register / LDS / code-size figures of the gfx950 kernels of ONE translation unit, from the device assembly
-# (no GPU needed).  usage: tools/kernel_info.sh render_bwd [kernel-name-substring] [extra hipcc flags...]
+# (no GPU needed).  usage: tools/kernel_info.sh render_bwd|render_bwd_strict|... [kernel-name-substring] [extra hipcc flags...]
 set -e
 SRC=$1; PAT=${2:-.}; shift; shift || true
 cd "$(dirname "$0")/../bloomscene_amd/csrc"

@@ -29,10 +29,10 @@ def main():
             pass
         rec = {"point": name, "bwd_batch": batch, "ms_per_step": b["ms_per_step"], "Msplats_per_s": b["value"],
                "stage_ms": {k: b["stage_ms"][k] for k in ("render_fwd", "render_bwd")}}
-        # (template arguments follow the name; the backward is k_render_bwd<DEPTH, STRICT> on long-list frames such as C5
-        #  and k_render_bwd_t<DEPTH> otherwise: whichever the run launched)
+        # (template arguments follow the name; the backward is k_render_bwd_t<DEPTH, NS>, or k_render_bwd_strict<DEPTH> in
+        #  a --strict-gradients run: whichever the run launched)
         for key, kerns in (("render_fwd", ("bsr::k_render_fwd<",)),
-                           ("render_bwd", ("bsr::k_render_bwd<false", "bsr::k_render_bwd_t<false"))):
+                           ("render_bwd", ("bsr::k_render_bwd_t<false", "bsr::k_render_bwd_strict<false"))):
             r = next((v for k, v in pmc.items() if k.startswith(kerns)), None)
             if r is not None:
                 rec.setdefault("kernels", {})[key] = next(k for k in pmc if k.startswith(kerns))
