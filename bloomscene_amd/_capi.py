@@ -1,6 +1,6 @@
 """ctypes binding of ``libbloomscene_rast.so`` (C ABI declared in ``include/bloomscene_rast.h``,
-``include/bloomscene_anchors.h``, ``include/bloomscene_grid.h``, ``include/bloomscene_knn.h`` and
-``include/bloomscene_densify.h``).
+``include/bloomscene_anchors.h``, ``include/bloomscene_grid.h``, ``include/bloomscene_knn.h``,
+``include/bloomscene_densify.h`` and ``include/bloomscene_entropy.h``).
 
 The library is built in-tree (``bloomscene_amd/csrc/Makefile``, hipcc --offload-arch=gfx950).
 There is deliberately NO fallback: if the shared object is missing or a call fails, this module
@@ -106,6 +106,12 @@ SIGNATURES = {
     "bsr_scatter_max": (C.c_int, [C.c_int] * 4 + [_F, _F, _F, C.c_longlong, C.c_longlong, _F, _F, C.c_void_p]),
     "bsr_voxel_isin_scratch_bytes": (C.c_size_t, [C.c_int]),
     "bsr_voxel_isin": (C.c_int, [C.c_int, C.c_int, _F, _F, _F, C.c_void_p, C.c_void_p]),
+    # include/bloomscene_entropy.h
+    "bsr_entropy_scratch_bytes": (C.c_size_t, [C.c_int] * 3),
+    "bsr_entropy_forward": (C.c_int, [C.c_int] * 3 + [_F, C.c_longlong] * 3 + [_F, C.c_int, _F, _F, _F] + [_F] * 4
+                            + [C.c_void_p, C.c_void_p]),
+    "bsr_entropy_backward": (C.c_int, [C.c_int] * 3 + [_F, C.c_longlong] * 3 + [_F, C.c_int, _F, _F, _F] + [_F, C.c_int]
+                             + [_F] * 5 + [C.c_void_p, C.c_void_p]),
 }
 
 _lib = None

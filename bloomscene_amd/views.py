@@ -9,7 +9,8 @@ talk on the data path.  Views are dealt round-robin so yaw-dependent load balanc
 ``render_view`` / ``prefilter`` reproduce the call shapes of ``gaussian_renderer.render`` and
 ``prefilter_voxel`` (reference ``gaussian_renderer/__init__.py:211-291,294-349``) for already
 decoded Gaussians; ``render_neural`` starts one step earlier, at the outputs of the anchor MLP heads
-(the MLPs, the context model and the entropy coder themselves are out of scope).
+(the MLPs, the context model and the entropy coder themselves are out of scope; the rate term of the loss the context
+model feeds, GR:100-127, is ``bloomscene_amd.entropy``).
 """
 from __future__ import annotations
 
@@ -382,7 +383,7 @@ def render_neural(cam: MiniCam, anchor, grid_scaling, grid_offsets, neural_opaci
     where the MLP heads have produced their outputs: fused anchor expansion (GR:165-203,
     ``neural_gaussians.expand_anchors``) -> rasterizer with ``colors_precomp`` and ``sh_degree=1``
     (GR:235-262).  Returns the training-mode result dict of GR:266-279 minus the entropy-coder rates
-    (``bit_per_*`` come from the out-of-scope context model): render, viewspace_points,
+    (``bit_per_*``: ``bloomscene_amd.entropy.context_rates`` from the context model's output): render, viewspace_points,
     visibility_filter, radii, depth, selection_mask, neural_opacity, scaling.  ``fused`` (default): one native call
     each way (``neural_gaussians.render_anchors``); False: expand_anchors and the rasterizer as separate autograd nodes.
     Either way ``viewspace_points.grad`` holds the screen-space gradient after backward."""
