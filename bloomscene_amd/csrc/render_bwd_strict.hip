@@ -4,10 +4,13 @@
 // cuda_rasterizer/backward.cu:399-586 of its depth-diff-gaussian-rasterization submodule.
 //
 // The reference's per-pair operations on the reference's operands (backward.cu:521,527-536,557,561-583): IEEE
-// divisions, no fp contraction, the pinned exp on every pair, accum_rec channel by channel, the per-pair terms summed as
-// they are -- only the ORDER of the nine sums then differs from the oracle's.  Until round 4 this walk (with the
-// arithmetic shortcuts of k_render_bwd_t switched on one by one through attribution builds: docs/EXPERIMENTS.md) was
-// also the default; ~2x the time of k_render_bwd_t.
+// divisions, no fp contraction, the pinned exp on every pair, accum_rec channel by channel, the background term as a
+// quotient and then a product (:557), the per-pair terms summed as they are -- only the ORDER of the nine sums then
+// differs from the oracle's.  The pin is tests/test_strict_backward_gpu.py: under an upstream kept at ONE pixel every sum
+// has at most one nonzero term and the nine accumulators equal the oracle's as values, DEPTH = false and DEPTH = true
+// (zero depth upstream) alike; an operation changed in pair_terms_reference has to keep that test passing.  Until round
+// 4 this walk (with the arithmetic shortcuts of k_render_bwd_t switched on one by one through attribution builds:
+// docs/EXPERIMENTS.md) was also the default; ~2x the time of k_render_bwd_t.
 //
 // The reference issues 9 lane-scattered float atomicAdds per pair.  On MI355X lane-scattered
 // global float atomics run ~17x below the contiguous rate (~20 G/s chip-wide), which would cap this
@@ -49,7 +52,7 @@ struct PairState {
 	float acc_rec[4], last_color[4], last_alpha;   // reference :527-536 channel by channel ([3] = depth, extension)
 };
 struct PixelConst {
-	float dpx0, dpx1, dpx2, neg_Tfinal_bg, gz, g1, ddelx_dx, ddely_dy;
+	float dpx0, dpx1, dpx2, neg_T_final, bg_dot_dpixel, gz, g1, ddelx_dx, ddely_dy;
 };
 // Per pair the reference adds (:574-583), with dL_dG = o * dL_dalpha:
 //   dL_dmean2D.x += dL_dG * dG_ddelx * ddelx_dx      dL_dconic.x += -0.5 gdx dx dL_dG
@@ -62,7 +65,6 @@ __device__ __forceinline__ void pair_terms_reference(PairState& st, const PixelC
                                                      const float alpha, float (&v)[10])
 {
 	const float om = 1.f - alpha;
-	const float inv = 1.0f / om;
 	st.T = st.T / om;   // reference :521
 	const float T = st.T;
 	// accum_rec = last_alpha * last_color + (1 - last_alpha) * accum_rec, then (c - accum_rec) * dL_dpixel.  A pair the
@@ -81,7 +83,8 @@ __device__ __forceinline__ void pair_terms_reference(PairState& st, const PixelC
 		else Sd = c4[ch] - st.acc_rec[ch];
 	}
 	st.last_alpha = live ? alpha : st.last_alpha;
-	const float dL_dalpha = T * S + px.neg_Tfinal_bg * inv;
+	// reference :557: a quotient, then a product ((-T_final * bg_dot) * (1 / om) rounds differently on ~40 % of pairs)
+	const float dL_dalpha = T * S + (px.neg_T_final / om) * px.bg_dot_dpixel;
 	const float ca = -2.0f * q0.z, cb = -q0.w, cc = -2.0f * q1.x;
 	const float gdx = G * dx, gdy = G * dy;
 	const float dG_ddelx = -gdx * ca - gdy * cb;
@@ -166,8 +169,8 @@ __global__ void __launch_bounds__(BSR_BLOCK) k_render_bwd_strict(int n_tiles, in
 		pc.dpx1 = dL_dpixels[plane + pix_id];
 		pc.dpx2 = dL_dpixels[2 * plane + pix_id];
 	}
-	const float bg_dot_dpixel = bg_color[0] * pc.dpx0 + bg_color[1] * pc.dpx1 + bg_color[2] * pc.dpx2;
-	pc.neg_Tfinal_bg = -T_final * bg_dot_dpixel;
+	pc.bg_dot_dpixel = bg_color[0] * pc.dpx0 + bg_color[1] * pc.dpx1 + bg_color[2] * pc.dpx2;
+	pc.neg_T_final = -T_final;
 	// depth extension: d_i = gz * z_i + g1 plays the role of a fourth colour channel
 	if (DEPTH && inside) {
 		const float depth_px = out_depth[pix_id];
