@@ -1,6 +1,6 @@
 """ctypes binding of ``libbloomscene_rast.so`` (C ABI declared in ``include/bloomscene_rast.h``,
 ``include/bloomscene_anchors.h``, ``include/bloomscene_grid.h``, ``include/bloomscene_knn.h``,
-``include/bloomscene_densify.h`` and ``include/bloomscene_entropy.h``).
+``include/bloomscene_densify.h``, ``include/bloomscene_entropy.h`` and ``include/bloomscene_loss.h``).
 
 The library is built in-tree (``bloomscene_amd/csrc/Makefile``, hipcc --offload-arch=gfx950).
 There is deliberately NO fallback: if the shared object is missing or a call fails, this module
@@ -112,6 +112,10 @@ SIGNATURES = {
                             + [C.c_void_p, C.c_void_p]),
     "bsr_entropy_backward": (C.c_int, [C.c_int] * 3 + [_F, C.c_longlong] * 3 + [_F, C.c_int, _F, _F, _F] + [_F, C.c_int]
                              + [_F] * 5 + [C.c_void_p, C.c_void_p]),
+    # include/bloomscene_loss.h
+    "bsr_photometric_scratch_bytes": (C.c_size_t, [C.c_int] * 4),
+    "bsr_photometric_forward": (C.c_int, [C.c_int] * 4 + [_F, _F, C.c_float, _F, _F, _F, C.c_void_p, C.c_void_p]),
+    "bsr_photometric_backward": (C.c_int, [C.c_int] * 4 + [_F, _F, _F, C.c_float, _F, _F, C.c_void_p]),
 }
 
 _lib = None
