@@ -1,6 +1,7 @@
 """ctypes binding of ``libbloomscene_rast.so`` (C ABI declared in ``include/bloomscene_rast.h``,
 ``include/bloomscene_anchors.h``, ``include/bloomscene_grid.h``, ``include/bloomscene_knn.h``,
-``include/bloomscene_densify.h``, ``include/bloomscene_entropy.h`` and ``include/bloomscene_loss.h``).
+``include/bloomscene_densify.h``, ``include/bloomscene_entropy.h``, ``include/bloomscene_loss.h`` and
+``include/bloomscene_depth_loss.h``).
 
 The library is built in-tree (``bloomscene_amd/csrc/Makefile``, hipcc --offload-arch=gfx950).
 There is deliberately NO fallback: if the shared object is missing or a call fails, this module
@@ -116,6 +117,12 @@ SIGNATURES = {
     "bsr_photometric_scratch_bytes": (C.c_size_t, [C.c_int] * 4),
     "bsr_photometric_forward": (C.c_int, [C.c_int] * 4 + [_F, _F, C.c_float, _F, _F, _F, C.c_void_p, C.c_void_p]),
     "bsr_photometric_backward": (C.c_int, [C.c_int] * 4 + [_F, _F, _F, C.c_float, _F, _F, C.c_void_p]),
+    # include/bloomscene_depth_loss.h
+    "bsr_depth_prior_scratch_bytes": (C.c_size_t, [C.c_int] * 2),
+    "bsr_depth_prior_forward": (C.c_int, [C.c_int] * 2 + [_F] * 3 + [C.c_longlong] * 3 + [C.c_int] + [C.c_float] * 3 + [C.c_int]
+                                + [_F] * 4 + [C.c_void_p]),
+    "bsr_depth_prior_backward": (C.c_int, [C.c_int] * 2 + [_F] * 3 + [C.c_longlong] * 3 + [C.c_int] + [C.c_float] * 3 + [C.c_int]
+                                 + [_F] * 4 + [C.c_void_p]),
 }
 
 _lib = None
