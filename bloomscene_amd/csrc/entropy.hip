@@ -80,11 +80,15 @@ struct EntropyElement {
 // -- any difference of two cdf values there cancels to d times their size, and the gradient of q is ~ 1 / q, largest exactly
 // there.  The first term left out is d^10 He_10(m) / 11!: below 3e-7 of the sum for |m| <= 6 (and at |m| = 6 the
 // likelihood of such a bin is under the floor).  Wider bins: from the side where neither term is near 1.
-// A NaN argument fails the first test and ends up in an erf: NaN.
+// For |m| >= 16 the narrow bin is a zero with the sign of d: expf(-u / 2) is exactly 0 from u = 208 on, so every
+// non-zero result is untouched, while he6 and he8 overflow from |m| ~ 6.6e4 on and 0 * inf would be a NaN (an infinite
+// m included; d = 0 gives 0 for every m).
+// A NaN argument fails the first two tests and ends up in the series or in an erf: NaN.
 __device__ __forceinline__ float cdf_difference(float tu, float tl, float m, float d)
 {
 	if (fabsf(d) <= 0.25f) {
 		const float u = m * m, d2 = d * d;
+		if (u >= 256.0f) return d * 0.0f;
 		const float he2 = u - 1.0f;
 		const float he4 = (u - 6.0f) * u + 3.0f;
 		const float he6 = ((u - 15.0f) * u + 45.0f) * u - 15.0f;
@@ -264,11 +268,13 @@ __global__ void __launch_bounds__(BSR_ENTROPY_BLOCK) k_entropy_bwd(EntropyOperan
 					diff = dl * expm1f(-ex);
 					tdiff = e.tu * diff + qs * dl;
 				}
-				const float gd = ga * diff;
+				// below the floor nothing flows, whatever tu and tl are (an overflowed tu makes tdiff inf * 0)
+				const bool open = l >= 1e-6f;
+				const float gd = open ? ga * diff : 0.0f;
 				if (dx) dx[i * a.C + j] = e.in_bounds ? gd : 0.0f;
 				if (dmean) dmean[i * a.C + j] = -gd;
-				if (dscale) dscale[i * a.C + j] = e.scale_ok ? -(ga * tdiff) : 0.0f;
-				const float dqv = ga * ((du + dl) * 0.5f);
+				if (dscale) dscale[i * a.C + j] = e.scale_ok && open ? -(ga * tdiff) : 0.0f;
+				const float dqv = open ? ga * ((du + dl) * 0.5f) : 0.0f;
 				if (dq && a.q_mode == BSR_ENTROPY_Q_ELEMENT) dq[i * a.C + j] = dqv;
 				dq_lane += (double)dqv;
 			}

@@ -25,9 +25,22 @@
  * and, where the bin is narrow, |q / 2s| <= 1/4 (there every difference of two cdf values cancels to q / s times their size,
  * and the gradient of q, about 1 / q, is at its largest), the integral of phi over the bin expanded at its centre m = c / s
  * with d = q / 2s:   2 d phi(m) sum_{k = 0..4} d^2k He_2k(m) / (2k + 1)!    (He_n the probabilists' Hermite polynomials; the
- * first term left out is below 3e-7 of the sum for |m| <= 6).  So the error of l is a few units in the last place OF l,
- * on the tails and for narrow bins as well.  Accuracy is judged against float64 (tests/entropy_reference.py), not against
- * the bits of the fp32 formula above.
+ * first term left out is below 3e-7 of the sum for |m| <= 6).  GUARD: for m m >= 256 the narrow bin is a zero with the sign
+ * of d and the series is not formed -- exp(-m m / 2) is exactly 0 in fp32 from m m = 208 on, so no non-zero result
+ * changes, while He_6 and He_8 overflow from |m| ~ 6.6e4 on and 0 * inf would be a NaN.  In particular d = 0 gives l = 0
+ * for every m, an infinite one included.  So the error of l is a few units in the last place OF l for |m| < 1, on the
+ * tails and for narrow bins as well; further out the fp32 roundings of c, tu, tl and m m themselves are multiplied by
+ * t^2.  The largest figures of this arithmetic, measured per region on the sweep of tests/test_entropy_cpu.py (table
+ * there and in docs/EXPERIMENTS.md), all at |m| in [4, 6): l 51 units of l; dx = -dmean 51, dq 45 and dscale 71 units of
+ * 2^-24 of the gradient's scale; the first-order bound is 2.5 t^2 + 16 = 122 at |t| = 6.5.  Of the series the last
+ * coefficient, 1 / 9!, is the least constrained by any test: its term is below 6e-7 of the sum wherever l >= 1e-6, so the
+ * suite would notice it wrong by a factor of about 30 or more, no less.
+ * Accuracy is judged against float64 (tests/entropy_reference.py), not against the bits of the fp32 formula above.
+ *
+ * OPERAND DOMAIN.  Finite operands may overflow c / s, tu or tl (mean = 1e30 over s = 1e-9): an infinite argument of Phi
+ * is legal, l is then 0, 1/2 or 1 as the formula gives.  Wherever l < 1e-6 EVERY gradient is exactly 0 whatever tu and tl
+ * are (no inf * 0): that covers every case in which tu and tl overflow to the same side.  With l >= 1e-6 and an infinite
+ * tu or tl (a bin wider than 3.4e38 s) the gradients are unspecified.
  *
  * GRADIENT for an upstream g of bits (gl is EM:43-50: its `g < 0` pass is cancelled by its own zeroing):
  *   gl = l >= 1e-6 ? -g / (l ln 2) : 0 ;  sg = sign(upper - lower), sign(0) = 0
@@ -41,7 +54,8 @@
  *   no gradient to x_mean.  With a weight, g of bits is (upstream of the product) * w.
  * du - dl is taken as -du expm1(e) (e <= 0) or dl expm1(-e) (e > 0) with e = (c / s)(q / s) = (tu^2 - tl^2) / 2, and
  * tu du - tl dl as t' (du - dl) + (q / s) d' with (t', d') the pair of the other side: no difference of two nearly equal
- * exponentials.  A NaN operand gives NaN bits; its gradient is unspecified.
+ * exponentials.  Below the floor (l < 1e-6) the four gradients are written as zeros without being formed.  A NaN operand
+ * gives NaN bits; its gradient is unspecified.
  *
  * ROWS.  With a row mask (GR:100-101 `choose_idx`) a row whose byte is 0 is skipped before its operands are loaded: it
  * contributes nothing to the sums and its gradient rows are written as zeros.  Gradients are always dense.

@@ -17,6 +17,7 @@ import torch
 import torch.nn.functional as F
 
 SCENES = ("smooth", "noise", "rendered", "flat")
+EDGE_SCENES = ("tied_M", "tied_wide", "near_flat")   # built for one branch each: scene() says which; not swept over every shape
 SK_HEX = {0: "0x1.02d50cp-4", 1: "0x1.c8d656p-5", 2: "0x1.93285p-5", 4: "0x1.39fab6p-5", 5: "0x1.1515f8p-5",
           8: "0x1.7ce05p-6"}     # BSR_DEPTH_PRIOR_SK* of the header
 
@@ -191,6 +192,7 @@ def evaluate(D, P, rgb, value=None, domin=None, smooth=None, normalise_depths=Tr
         if domin is not None:
             sd = f(np.sqrt(min(S, 1e6) + 1e-6))
             gate = (S <= 1e6) & (np.abs(r) <= f(1e6)) & (tt * tt <= f(1e6))
+            res.gate = gate
             Gd = np.where(gate, _sign(ec) * (tt / sd), f(0)).astype(f)
             G = G + f(domin) * Gd if value is not None else f(domin) * Gd
         if smooth is not None:
@@ -221,16 +223,76 @@ def evaluate(D, P, rgb, value=None, domin=None, smooth=None, normalise_depths=Tr
 
 
 # ---------------------------------------------------------------- scenes
+def tied_pixels(kind, H, W):
+    """-> (neg, pos): flat indices of the pixels with e = -M and with e = +M, at least two pixels from every border and
+    with disjoint 5 x 5 windows.  tied_M: 3 and 2.  tied_wide (80 x 80, four workgroups of 256 threads striding the
+    6400 pixels in the linear reductions): 5 and 4, and (index // 256) % 4 takes all four values in either list, so every
+    tie count has to be merged from four partials; the counts differ so that no two can be mistaken for each other."""
+    if kind == "tied_wide":
+        assert (H, W) == (80, 80)
+        chosen = []
+        for b, t in ((0, 1), (1, 2), (2, 3), (3, 5), (0, 3), (0, 5), (1, 3), (2, 1), (3, 0)):     # 256-pixel chunk 4 t + b
+            chosen.append(next(at for at in range(256 * (4 * t + b) + 11 * len(chosen), 256 * (4 * t + b + 1))
+                               if 2 <= at // W < H - 3 and 2 <= at % W < W - 3
+                               and all(max(abs(at // W - c // W), abs(at % W - c % W)) >= 5 for c in chosen)))
+        neg, pos = chosen[:5], chosen[5:]
+    else:
+        assert H >= 15 and W >= 15
+        cells = [(H // 4, W // 4), (H // 4, 3 * W // 4), (H // 2, W // 2), (3 * H // 4, W // 4), (3 * H // 4, 3 * W // 4)]
+        flat = [y * W + x for y, x in cells]
+        neg, pos = flat[0::2], flat[1::2]
+    for at in neg + pos:
+        y, x = divmod(at, W)
+        assert 2 <= y < H - 3 and 2 <= x < W - 3, (at, y, x)
+    for a in neg + pos:
+        for b in neg + pos:
+            assert a == b or max(abs(a // W - b // W), abs(a % W - b % W)) >= 5, (a, b)
+    return neg, pos
+
+
+def clamp_gate_scene():
+    """B3 of the clamp gates: -> (D, P) float32 [5, 5] for the distribution term alone without normalisation.  D lies
+    beyond +-1e6 at three pixels, exactly at +1e6 and at -1e6 at one each; P is within 150 of the clamped D, so S < 1e6."""
+    rng = np.random.RandomState(5)
+    D = rng.uniform(-3, 3, (5, 5))
+    D[0, 0], D[1, 2], D[4, 4], D[2, 2], D[3, 1] = 2e6, -5e6, 1.5e6, 1e6, -1e6
+    P = np.clip(D, -1e6, 1e6) + rng.uniform(20, 150, (5, 5)) * rng.choice([-1.0, 1.0], (5, 5))
+    return (torch.from_numpy(a.astype(np.float32)) for a in (D, P))
+
+
 def scene(kind, H, W, seed=1):
     """-> (D, P, rgb): float32 torch tensors [H, W], [H, W], [H, W, 3].
+    tied_M / tied_wide: D and P both span exactly [0, 4]; at the pixels tied_pixels() names D = 0, P = 4 (e = -o_max) or
+    D = 4, P = 0 (e = +r_max), everywhere else both lie in [1, 3]: |r - o| (and |D - P|) is the SAME expression of the
+    same values on all of them, bit-identical in any precision, and at most half of it elsewhere.  They are the tied
+    minima and maxima of D and of P as well.  Around each, D is 2 on the 5 x 5 window and rgb one colour on the 2 x 2
+    block: the pixels of one sign have one gradient, bit for bit.
+    near_flat: D takes the four fp32 values 2 + k 2^-22, a range of three units of the value; P as in "smooth".
     smooth / noise / rendered: one pixel of P is raised well above the rest where D is lowest, so that the maximum of
     |r - o| (normalised or not) is unique and far from the runner-up in float32 and float64 alike.
     rendered: a block of exact zeros in D (the pixels a rasterizer leaves empty: tied minima) and two pixels sharing the
     maximum.  flat: D and P constant (M = 0: HuberL1's 0 / 0 branch exists and must never be selected)."""
-    rng = np.random.RandomState(1000 * seed + 7 * H + W + 31 * SCENES.index(kind))
+    rng = np.random.RandomState(1000 * seed + 7 * H + W + 31 * (SCENES + EDGE_SCENES).index(kind))
     ys, xs = np.mgrid[0:H, 0:W].astype(np.float64)
     u, v = ys / max(H - 1, 1), xs / max(W - 1, 1)
-    if kind == "flat":
+    if kind in ("tied_M", "tied_wide"):
+        D = 1.0 + 2.0 * rng.rand(H, W)
+        P = 1.0 + 2.0 * rng.rand(H, W)
+        rgb = rng.rand(H, W, 3)
+        neg, pos = tied_pixels(kind, H, W)
+        for at, (dv, pv) in [(a, (0.0, 4.0)) for a in neg] + [(a, (4.0, 0.0)) for a in pos]:
+            y, x = divmod(at, W)
+            D[y - 2:y + 3, x - 2:x + 3] = 2.0
+            D[y, x], P[y, x] = dv, pv
+            rgb[y:y + 2, x:x + 2] = 0.5
+    elif kind == "near_flat":
+        D = (np.float32(2.0) + np.float32(2.0 ** -22) * rng.randint(0, 4, (H, W)).astype(np.float32)).astype(np.float64)
+        P = 1.5 + 0.9 * np.cos(2.5 * u - v) + 0.5 * v + 0.01 * rng.rand(H, W)
+        rgb = rng.rand(H, W, 3)
+        k = np.unravel_index(np.argmin(D), D.shape)
+        P[D == D.max()] = P.max()
+        P[k] = P.max() + 0.75 * (P.max() - P.min()) + 1.0
+    elif kind == "flat":
         D = np.full((H, W), 1.75)
         P = np.full((H, W), 0.5)
         rgb = rng.rand(H, W, 3)

@@ -9,7 +9,7 @@ import numpy as np
 import torch
 
 WINDOW_HEX = ("0x1.0d956cp-10", "0x1.f1fe02p-8", "0x1.26eb18p-5", "0x1.bff0fep-4", "0x1.b43c3ep-3", "0x1.10656p-2")
-SCENES = ("noise", "smooth", "flat")
+SCENES = ("noise", "smooth", "flat", "hdr")
 
 
 def window(dtype=np.float32):
@@ -80,7 +80,9 @@ def evaluate(img, gt, lam, dtype=np.float32, g=1.0):
 def scene(kind, B, C, H, W, seed=1):
     """-> (img, gt) float32 [B, C, H, W] torch tensors on the CPU.
     noise: two independent uniform images.  smooth: gt = 0.5 + 0.4 sin(7x + 3y), 0.5 + 0.4 cos(5y), x y (by channel % 3) on
-    the unit square, img = clamp(gt + 0.03 randn).  flat: gt = 0.9, img = gt + 1e-3 randn in the lower half, = gt above."""
+    the unit square, img = clamp(gt + 0.03 randn).  flat: gt = 0.9, img = gt + 1e-3 randn in the lower half, = gt above.
+    hdr: an unclamped render against a target in [0, 1]: gt uniform, img = gt + 1.5 randn held to [-2, 6]; nothing in the
+    formula or the kernels assumes [0, 1]."""
     gen = torch.Generator().manual_seed(seed)
     if kind == "noise":
         return torch.rand(B, C, H, W, generator=gen), torch.rand(B, C, H, W, generator=gen)
@@ -95,4 +97,7 @@ def scene(kind, B, C, H, W, seed=1):
         img = gt + 1e-3 * torch.randn(B, C, H, W, generator=gen)
         img[:, :, :H // 2] = gt[:, :, :H // 2]
         return img, gt
+    if kind == "hdr":
+        gt = torch.rand(B, C, H, W, generator=gen)
+        return (gt + 1.5 * torch.randn(B, C, H, W, generator=gen)).clamp(-2, 6), gt
     raise ValueError(kind)

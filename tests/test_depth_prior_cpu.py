@@ -269,3 +269,111 @@ def test_scratch_sizing_and_entry_points():
         assert n % 256 == 0 and n == 256 + 1024 * 32 + -(-min(tiles(H, W), 16384) * 40 // 256) * 256
     assert lib.bsr_depth_prior_scratch_bytes(0, 5) == 0 and lib.bsr_depth_prior_scratch_bytes(5, -1) == 0
     assert lib.bsr_depth_prior_scratch_bytes(1 << 16, 1 << 15) == 0
+
+
+# ---------------------------------------------------------------- the scenes built for one branch each (DR.EDGE_SCENES)
+TIED = (("tied_M", (17, 33), 3, 2), ("tied_M", (37, 53), 3, 2), ("tied_wide", (80, 80), 5, 4))
+
+
+@pytest.mark.parametrize("kind,shape,n_neg,n_pos", TIED, ids=lambda v: "x".join(map(str, v)) if isinstance(v, tuple) else str(v))
+def test_tied_scenes_have_the_ties_they_were_built_for(kind, shape, n_neg, n_pos):
+    """What the GPU tests of the tied maximum rely on, so that none passes vacuously: cnt_M, cnt_min, cnt_max in fp32 and
+    float64 alike, both signs of e at the tied pixels, the runner-up at half of M at most, one gradient per sign class in
+    the fp32 evaluation of the header, the header's equal shares equal to float64 autograd (torch.max splits the gradient
+    of a tied maximum evenly) -- and for tied_wide every tie spread over the four workgroups of the linear reductions."""
+    D, P, rgb = DR.scene(kind, *shape)
+    neg, pos = DR.tied_pixels(kind, *shape)
+    assert (len(neg), len(pos)) == (n_neg, n_pos)
+    d, p = D.numpy().reshape(-1), P.numpy().reshape(-1)
+    assert d.min() == 0 and d.max() == 4 and p.min() == 0 and p.max() == 4
+    assert sorted(np.flatnonzero(d == 0)) == sorted(neg) == sorted(np.flatnonzero(p == 4))
+    assert sorted(np.flatnonzero(d == 4)) == sorted(pos) == sorted(np.flatnonzero(p == 0))
+    if kind == "tied_wide":
+        assert shape[0] * shape[1] > 3 * 2048                      # four workgroups (BSR_DEPTH_LIN_PER_BLOCK pixels each)
+        for group in (neg, pos):
+            assert {(i // 256) % 4 for i in group} == {0, 1, 2, 3}
+    else:
+        assert shape[0] * shape[1] <= 2048
+    for norm in (True, False):
+        for cfg in ("all", "value"):
+            w = WEIGHTS[cfg]
+            ref = DR.autograd64(D, P, rgb, *w, norm)
+            for dt in (np.float64, np.float32):
+                ev = DR.evaluate(*_np(D, P, rgb), *w, norm, dt=dt)
+                assert ev.cnt_M == n_neg + n_pos >= 5
+                if norm:
+                    assert (ev.cnt_min, ev.cnt_max) == (n_neg, n_pos)
+                e = (ev.r - ev.o).reshape(-1)
+                assert (e[neg] == -ev.M).all() and (e[pos] == ev.M).all() and ev.M > 0
+                others = np.ones(e.size, bool)
+                others[neg + pos] = False
+                assert np.abs(e[others]).max() <= 0.5 * ev.M
+                g = ev.grad.reshape(-1)
+                for group in (neg, pos):
+                    assert (g[group] == g[group[0]]).all() and g[group[0]] != 0
+                if dt == np.float64:
+                    assert Hh.max_err_over_scale(ev.grad, ref.grad) <= F64_TOL, (norm, cfg)
+
+
+def test_clamp_gate_scenes_open_and_close_the_gates_they_were_built_for():
+    """The distribution term alone, no normalisation.  5 x 5: S < 1e6 (the sum gate is open), the three pixels beyond
+    +-1e6 are closed by |r| <= 1e6, the two exactly at the bound are open -- torch.clamp passes the gradient at the bound
+    -- like everything else.  1 x 1 with D = 2000, P = 0: S is exactly 1e6, open, and the pixel's own t t <= 1e6 is
+    closed; no other input separates the two gates."""
+    D, P = DR.clamp_gate_scene()
+    rgb = torch.zeros(5, 5, 3)
+    beyond = np.zeros((5, 5), bool)
+    beyond[0, 0] = beyond[1, 2] = beyond[4, 4] = True
+    assert (np.abs(D.numpy()) > 1e6).sum() == 3 and (np.abs(D.numpy())[beyond] > 1e6).all()
+    assert D[2, 2].item() == 1e6 and D[3, 1].item() == -1e6
+    ref = DR.autograd64(D, P, rgb, None, 1.0, None, False)
+    for dt in (np.float64, np.float32):
+        ev = DR.evaluate(*_np(D, P, rgb), None, 1.0, None, False, dt=dt)
+        assert ev.S < 1e6 and (ev.gate == ~beyond).all()
+        assert not ev.grad[beyond].any() and ev.grad[~beyond].all()
+    assert not ref.grad[beyond].any() and ref.grad[2, 2] != 0 and ref.grad[3, 1] != 0
+    assert Hh.max_err_over_scale(DR.evaluate(*_np(D, P, rgb), None, 1.0, None, False, dt=np.float64).grad, ref.grad) <= F64_TOL
+    one = DR.evaluate(np.full((1, 1), 2000.0), np.zeros((1, 1)), np.zeros((1, 1, 3)), None, 1.0, None, False, dt=np.float32)
+    assert one.S == 1e6 and not one.gate.any() and not one.grad.any()
+    ref = DR.autograd64(torch.full((1, 1), 2000.0), torch.zeros(1, 1), torch.zeros(1, 1, 3), None, 1.0, None, False)
+    assert not ref.grad.any() and abs(ref.out[2] - (np.sqrt(1e6 + 1e-6) + 4 * np.sqrt(1e-12 + 1e-6))) <= 1e-9
+
+
+@pytest.mark.parametrize("shape", ((1, 1), (1, 40), (40, 1), (2, 40)), ids=lambda s: "x".join(map(str, s)))
+def test_thin_shapes_without_the_value_term(shape):
+    """H = 1 or W = 1 is legal with the value term off: the header's gather of A2 then has both border rules on at once."""
+    for kind in ("noise", "rendered"):
+        D, P, rgb = DR.scene(kind, *shape)
+        ref = DR.autograd64(D, P, rgb, None, 0.3, 1.9, True)
+        got = DR.evaluate(*_np(D, P, rgb), None, 0.3, 1.9, True, dt=np.float64)
+        assert Hh.max_err_over_scale(got.grad, ref.grad) <= F64_TOL or not ref.grad.any()
+        assert np.abs(got.grad - ref.grad).max() <= F64_TOL * max(np.abs(ref.grad).max(), 1.0)
+        for a, b in zip(got.out, ref.out):
+            assert abs(a - b) <= F64_TOL * max(abs(b), 1.0)
+
+
+def test_native_entry_points_refuse_the_value_term_on_a_thin_shape_with_the_headers_words():
+    import threading
+    lib = _capi.lib()
+    seen = []
+
+    def calls():             # (the error string belongs to the calling thread: this one's dies with it)
+        for H, W in ((1, 40), (40, 1), (1, 1)):
+            for fn in (lib.bsr_depth_prior_forward, lib.bsr_depth_prior_backward):
+                rc = fn(H, W, None, None, None, 0, 0, 0, 1 | 4, 1.0, 1.0, 1.0, 1, None, None, None, None, None)
+                seen.append((rc, f"the value term needs H, W >= 2 (got {H}, {W})" in _capi.last_error()))
+
+    t = threading.Thread(target=calls)
+    t.start()
+    t.join()
+    assert seen == [(1, True)] * 6, seen
+
+
+def test_near_flat_scene_spans_three_units_of_the_depth():
+    for shape in ((17, 33), (37, 53)):
+        D, P, rgb = DR.scene("near_flat", *shape)
+        d = D.numpy()
+        assert d.max() - d.min() == 3 * np.spacing(np.float32(2.0)) and len(np.unique(d)) == 4
+        ev = DR.evaluate(*_np(D, P, rgb), 0.7, 0.3, 1.9, True, dt=np.float32)
+        assert ev.cnt_M == 1 and ev.cnt_min > 50 and ev.cnt_max > 50
+        assert abs(float(d.max() - d.min()) / 1e-8 - 71.5) < 1          # (the 1e-8 of the range is 1.4 % of it)

@@ -31,7 +31,8 @@ SMALL = ((2, 2), (3, 5), (5, 5), (TH, TW), (TH + 1, TW + 1), (37, 53), (2 * TH +
 BIG = (512, 512)
 KINDS = ("smooth", "noise", "rendered")          # (flat has its own test: float64 autograd is 0 / 0 there)
 W3 = (0.7, 0.3, 1.9)
-CONFIGS = {"all": W3, "value": (0.7, None, None), "domin": (None, 0.3, None), "smooth": (None, None, 1.9)}
+CONFIGS = {"all": W3, "value": (0.7, None, None), "domin": (None, 0.3, None), "smooth": (None, None, 1.9),
+           "ds": (None, 0.3, 1.9)}
 FLOOR = 2.0 ** -23
 
 
@@ -426,3 +427,145 @@ def test_end_to_end_through_the_rasterizer():
     if loss0.requires_grad:
         loss0.backward()
     assert m.grad is None or not m.grad.any().item()
+
+
+# ---------------------------------------------------------------- the branches no typical scene enters (DR.EDGE_SCENES)
+TIED = (("tied_M", (TH + 1, TW + 1)), ("tied_M", (37, 53)), ("tied_wide", (80, 80)))
+
+
+def _check_maps(s, norm=True):
+    """r, o, h of the kernels bit for bit with the numpy evaluation of the header -> that evaluation"""
+    r, o, h, _ = (t.cpu().numpy() for t in _L().depth_prior_maps(s.Dd, s.Pd, s.rgbd, normalise=norm))
+    ev = DR.evaluate(s.D.numpy(), s.P.numpy(), s.rgb.numpy(), *W3, norm, dt=np.float32)
+    for name, got, want in (("r", r, ev.r), ("o", o, ev.o), ("h", h, ev.h)):
+        assert np.isfinite(want).all() and (_bits(got) == _bits(want)).all(), (name, float(np.abs(got - want).max()))
+    return ev
+
+
+def _check_total(label, c, mask):
+    """the sum of the gradient over ``mask`` against float64, in the form of test_tied_minima_get_identical_shares"""
+    exact, got, eager = c.ref.grad[mask].sum(), c.grad[mask].astype(np.float64).sum(), c.eager_grad[mask].astype(np.float64).sum()
+    bound = 2 * abs(eager - exact) + FLOOR * np.abs(c.ref.grad[mask]).sum()
+    print(f"{label}: kernel {got!r} eager {eager!r} float64 {exact!r}")
+    assert abs(got - exact) <= bound, label
+
+
+@pytest.mark.parametrize("norm", (True, False), ids=("normalised", "raw"))
+@pytest.mark.parametrize("cfg", ("all", "value"))
+@pytest.mark.parametrize("kind,shape", TIED, ids=lambda v: _ids(v) if isinstance(v, tuple) else v)
+def test_tied_maximum_of_the_value_term(kind, shape, cfg, norm):
+    """cnt_M >= 2 with both signs of e: the qM share at every l1 == M.  The tied pixels are also the tied minima and maxima
+    of D and P; in tied_wide each of those ties is merged from the partials of four workgroups (scene and counts:
+    test_depth_prior_cpu.py).  The gradient is one bit pattern per sign class; its total over each class, the gradient
+    everywhere and the scalars are held against float64 by the measure of this file; with normalisation the shares of
+    the tied extrema as well."""
+    c = _case(shape, kind, cfg, norm)
+    s = c.s
+    neg, pos = DR.tied_pixels(kind, *shape)
+    ev = _check_maps(s, norm)
+    assert ev.cnt_M == len(neg) + len(pos) >= 5
+    if norm:
+        assert (ev.cnt_min, ev.cnt_max) == (len(neg), len(pos))
+    e = (ev.r - ev.o).reshape(-1)
+    assert (e[neg] == -ev.M).all() and (e[pos] == ev.M).all()
+    _check_scalars(f"{shape} {kind} {cfg} norm={norm}", c.out, c.eager_out, c.ref.out)
+    print(f"gradient {shape} {kind} {cfg} norm={norm}: kernel {c.err:.3e} eager {c.eager_err:.3e}")
+    assert np.isfinite(c.grad).all() and c.err <= 2 * c.eager_err + FLOOR
+    g = c.grad.reshape(-1)
+    for name, group in (("e = -M", neg), ("e = +M", pos)):
+        assert (_bits(g[group]) == _bits(g[group])[0]).all() and g[group[0]] != 0, name
+        mask = np.zeros(g.size, bool)
+        mask[group] = True
+        _check_total(f"tied total {shape} {kind} {cfg} norm={norm} {name}", c, mask.reshape(shape))
+    if norm:
+        # what the normalisation adds on top of G / range at the tied extrema: the equal shares
+        ev64 = DR.evaluate(s.D.numpy(), s.P.numpy(), s.rgb.numpy(), *CONFIGS[cfg], True, dt=np.float64)
+        direct = (ev64.G / 4.00000001).reshape(-1)
+        for group, share in ((neg, ev64.share_min), (pos, ev64.share_max)):
+            exact = c.ref.grad.reshape(-1)[group[0]] - direct[group[0]]
+            assert abs(exact - share) <= 1e-11 * max(abs(c.ref.grad.reshape(-1)[group[0]]), abs(share))
+            got, eager = float(g[group[0]]) - direct[group[0]], float(c.eager_grad.reshape(-1)[group[0]]) - direct[group[0]]
+            assert abs(got - exact) <= 2 * abs(eager - exact) + FLOOR * abs(c.ref.grad.reshape(-1)[group[0]])
+
+
+def test_clamp_gates_of_the_distribution_term_pixel_by_pixel():
+    """The per-pixel gates |r| <= 1e6 and t t <= 1e6 (scenes and memberships: test_depth_prior_cpu.py): beyond the bound the
+    gradient is exactly 0, at the bound and elsewhere it is float64 autograd's (torch.clamp passes it at the bound)."""
+    D, P = DR.clamp_gate_scene()
+    w = CONFIGS["domin"]
+    ref = DR.autograd64(D, P, torch.zeros(5, 5, 3), *w, False)
+    eager_out, eager_grad = _eager(D.to(DEV), P.to(DEV), torch.zeros(5, 5, 3, device=DEV), w, False)
+    out, grad = _run(D.to(DEV), P.to(DEV), None, w, False)
+    beyond = np.abs(D.numpy()) > 1e6
+    assert beyond.sum() == 3 and not grad[beyond].any() and grad[~beyond].all()
+    assert grad[2, 2] != 0 and grad[3, 1] != 0
+    _check_scalars("clamp gates 5x5", out, eager_out, ref.out)
+    err, eager_err = Hh.max_err_over_scale(grad, ref.grad), Hh.max_err_over_scale(eager_grad, ref.grad)
+    print(f"gradient clamp gates 5x5: kernel {err:.3e} eager {eager_err:.3e}")
+    assert err <= 2 * eager_err + FLOOR
+    # S == 1e6 exactly: the sum gate is open, the pixel's own gate is closed
+    one_D, one_P = torch.full((1, 1), 2000.0, device=DEV), torch.zeros(1, 1, device=DEV)
+    out, grad = _run(one_D, one_P, None, w, False)
+    want = np.sqrt(1e6 + 1e-6) + 4 * np.sqrt(float(np.float32(1e-6)) ** 2 + 1e-6)
+    assert abs(float(out[2]) - want) <= _unit(want) and out[1] == 0 and out[3] == 0
+    assert grad.shape == (1, 1) and grad[0, 0] == 0
+
+
+@pytest.mark.parametrize("kind", ("noise", "rendered"))
+@pytest.mark.parametrize("shape", ((1, 1), (1, 40), (40, 1), (2, 40)), ids=_ids)
+def test_thin_shapes_without_the_value_term(shape, kind):
+    """H = 1 or W = 1 with smoothness + distribution: in the border form of A2 both gy == 0 and gy == H - 1 hold.  (The
+    maps call forms h, a value-term quantity, so it exists from 2 x 2 on: checked at (2, 40).)"""
+    c = _case(shape, kind, "ds")
+    _check_scalars(f"{shape} {kind} thin", c.out, c.eager_out, c.ref.out)
+    assert c.out[1] == 0 and c.grad.shape == shape and np.isfinite(c.grad).all()
+    print(f"gradient {shape} {kind} thin: kernel {c.err:.3e} eager {c.eager_err:.3e}")
+    if np.abs(c.ref.grad).max() > 0:
+        assert c.err <= 2 * c.eager_err + FLOOR
+    else:
+        assert not c.grad.any()
+    if min(shape) >= 2:
+        _check_maps(c.s)
+    else:
+        with pytest.raises(ValueError, match="at least 2"):
+            _run(c.s.Dd, c.s.Pd, c.s.rgbd)
+
+
+def test_grid_stride_of_the_tiled_kernels():
+    """(16 * 16385, 2): 16385 tiles of two pixels' width for at most 16384 workgroups, so workgroup 0 walks a second tile.
+    All three terms at once (float64 autograd through unfold takes about a second at this size)."""
+    shape = (16 * 16385, 2)
+    c = _case(shape, "noise")
+    _check_maps(c.s)
+    _check_scalars(f"{shape} noise", c.out, c.eager_out, c.ref.out)
+    print(f"gradient {shape}: kernel {c.err:.3e} eager {c.eager_err:.3e}")
+    assert np.isfinite(c.grad).all() and c.err <= 2 * c.eager_err + FLOOR
+    last = slice(16 * 16384, None)                      # the wrapped tile, on its own
+    assert Hh.max_err_over_scale(c.grad[last], c.ref.grad[last]) <= 2 * Hh.max_err_over_scale(c.eager_grad[last], c.ref.grad[last]) + FLOOR
+
+
+@pytest.mark.parametrize("shape", ((TH + 1, TW + 1), (37, 53)), ids=_ids)
+def test_near_flat_depth(shape):
+    """max - min of D is three fp32 units of D: the 1e-8 of the range is 1.4 % of it."""
+    for cfg, norm in (("all", True), ("value", True), ("smooth", True)):
+        c = _case(shape, "near_flat", cfg, norm)
+        _check_scalars(f"{shape} near_flat {cfg}", c.out, c.eager_out, c.ref.out)
+        print(f"gradient {shape} near_flat {cfg}: kernel {c.err:.3e} eager {c.eager_err:.3e}")
+        assert np.isfinite(c.grad).all() and c.err <= 2 * c.eager_err + FLOOR
+    _check_maps(_scene(shape, "near_flat"))
+
+
+@pytest.mark.parametrize("bad", (float("nan"), float("inf")), ids=("nan", "inf"))
+def test_non_finite_depth_gives_nan_scalars_and_leaves_no_state(bad):
+    """The header's deviation 1: no asserts, a NaN (or inf) pixel of D gives NaN scalars and the call returns.  Nothing
+    survives it: the same clean call before and after is bit-equal.  (Nothing is said about the gradient.)"""
+    s = _scene((37, 53), "noise")
+    before = _run(s.Dd, s.Pd, s.rgbd)
+    D = s.Dd.clone()
+    D[11, 17] = bad
+    out, grad = _run(D, s.Pd, s.rgbd)
+    torch.cuda.synchronize()
+    assert np.isnan(out).all(), out
+    after = _run(s.Dd, s.Pd, s.rgbd)
+    assert np.isfinite(after[0]).all()
+    assert (_bits(before[0]) == _bits(after[0])).all() and (_bits(before[1]) == _bits(after[1])).all()

@@ -105,6 +105,7 @@ def test_float64_restatement_is_the_conv2d_formula(kind):
         assert e_map <= 1e-10 and e_loss <= 1e-10 and e_grad <= 1e-10
         # The rounded window: each of the five moments moves by at most 2^-24 of a sum of non-negative terms <= 1 (the
         # inputs are in [0, 1.01]), and the map amplifies a moment's error by at most 1 / C2 + 2 / C1 < 3.3e4 / 1.5.
+        # (hdr: second moments up to 36, but variances of order 1 in place of C2: measured below 1e-6, far inside.)
         w_map, w_loss, w_grad = _errors(r, c["rounded_window"])
         print(f"  ... against the float32-rounded 2-D window: map {w_map:.3g} loss {w_loss:.3g} grad/max|grad| {w_grad:.3g}")
         assert w_map <= 5 * 2.0 ** -24 * 3.3e4 and w_loss <= w_map + 1e-10
@@ -121,6 +122,7 @@ def test_fp32_restatement_is_no_further_from_float64_than_eager_conv2d(kind):
         noise    2.5e-6             6.5e-6       3.8e-7                  1.1e-6
         smooth   2.6e-4             8.0e-4       5.6e-5                  1.5e-4
         flat     5.1e-4             2.0e-3       2.6e-4                  4.9e-4
+        hdr      2.6e-7             6.7e-7       1.3e-7                  2.9e-7
     """
     for which in ("exact window products", "float32-rounded window products"):
         ours_map = ours_grad = eager_map = eager_grad = 0.0

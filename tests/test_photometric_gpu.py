@@ -5,8 +5,10 @@ lines).
 
 Shapes (B, C, H, W), relative to the kernels' tile of 32 x 16 pixels: one pixel; every tap but a few in the padding; one
 full window; exactly one tile; one pixel over the tile in both directions; a ragged multi-tile shape with B > 1 whose
-halos cross tile edges both ways; narrow and tall (three tile rows, one ragged); and [3, 512, 512] once, 1536 workgroups
-for the ticket.  Inputs: the three scene kinds of the restatement.  Every (shape, scene) is evaluated once and shared."""
+halos cross tile edges both ways; narrow and tall (three tile rows, one ragged); [3, 512, 512] once, 1536 workgroups
+for the ticket; and 8193 small planes of two tiles once, two tiles more than there are workgroups, so that the first two
+workgroups walk on to a second tile with a halo to stage (the grid-stride path).  Inputs: the scene kinds of the
+restatement, "hdr" with values in [-2, 6] among them.  Every (shape, scene) is evaluated once and shared."""
 import functools
 from types import SimpleNamespace
 
@@ -24,7 +26,9 @@ LAMBDA = 0.2
 SMALL = ((1, 1, 1, 1), (1, 3, 3, 4), (1, 3, 11, 11), (1, 3, TH, TW), (1, 3, TH + 1, TW + 1), (2, 3, 37, 53),
          (1, 3, 2 * TH + 3, 5))
 BIG = (1, 3, 512, 512)
-CASES = [(s, k) for s in SMALL for k in PR.SCENES] + [(BIG, "noise")]
+MAX_BLOCKS = 16384   # BSR_LOSS_MAX_BLOCKS: more tiles than this and a workgroup walks several
+STRIDE = (2731, 3, 17, 5)   # 8193 planes of two tiles, the lower one ragged with the upper one's rows in its halo: 16386 tiles
+CASES = [(s, k) for s in SMALL for k in PR.SCENES] + [(BIG, "noise"), (STRIDE, "noise")]
 
 
 def _L():
@@ -85,6 +89,17 @@ def test_scalars_within_one_unit_of_the_exact_sums_and_repeatable(case):
         assert abs(float(got) - exact) <= unit, (name, float(got), exact)
     assert (_bits(c.out) == _bits(c.out_again)).all()
     assert (_bits(c.grad) == _bits(c.grad_again)).all()
+
+
+def test_the_grid_stride_shape_has_more_tiles_than_workgroups():
+    B, C, H, W = STRIDE
+    per_plane = -(-H // TH) * -(-W // TW)
+    assert per_plane > 1 and H % TH and B * C * per_plane > MAX_BLOCKS
+    c = _case(STRIDE, "noise")
+    wrapped = c.grad.reshape(B * C, H, W)[(MAX_BLOCKS // per_plane):]      # the planes whose tiles are second tiles
+    assert wrapped.shape[0] >= 1 and np.abs(wrapped).min() > 0
+    lib = __import__("bloomscene_amd._capi", fromlist=["lib"]).lib()
+    assert lib.bsr_photometric_scratch_bytes(B, C, H, W) == lib.bsr_photometric_scratch_bytes(1, 1, MAX_BLOCKS * TH, TW)
 
 
 @pytest.mark.parametrize("case", [((2, 3, 37, 53), "smooth"), ((1, 3, TH + 1, TW + 1), "flat")], ids=_ids)
