@@ -436,8 +436,9 @@ def training_view(cam: MiniCam, anchor, anchor_scaling, anchor_rotation, grid_of
     their six nonzero() passes and host synchronisations (the per-iteration half).
 
     ``anchor [N,3]``, ``anchor_scaling [N,6]``, ``anchor_rotation [N,4]``, ``grid_offsets [N,K,3]`` are the full
-    per-anchor parameters; ``heads(idx)`` is the caller's (out-of-scope) MLP evaluation and returns
-    ``(neural_opacity [n*K,1], color [n*K,3], scale_rot [n*K,7])`` for the ``n`` visible anchors ``idx``.
+    per-anchor parameters; ``heads(idx)`` is the caller's MLP evaluation and returns
+    ``(neural_opacity [n*K,1], color [n*K,3], scale_rot [n*K,7])`` for the ``n`` visible anchors ``idx`` -- natively,
+    ``bloomscene_amd.heads.AnchorHeads(mlp_opacity, mlp_cov, mlp_color, feat=, anchor=, camera_center=, offset_mask=)``.
     Returns render_neural's dict plus ``visible_mask`` (= prefilter_voxel's result), ``visible_idx`` and
     ``anchor_radii``; every output is bit-identical to the separate calls (tests/test_anchors_gpu.py)."""
     from .neural_gaussians import expand_anchors, render_anchors
