@@ -234,8 +234,10 @@ class EntropyGaussian(nn.Module):
 
 
 def context_rates(feat, grid_scaling, grid_offsets, context, choose, grid_masks, mask_anchor_rate, feat_mean,
-                  scaling_mean, offsets_mean, feat_dim, n_offsets, q_feat=0.25, q_scaling=2.5e-4, q_offsets=5e-2):
-    """GR:77-84 and GR:100-127 over three ``rate_sum`` calls.
+                  scaling_mean, offsets_mean, feat_dim, n_offsets, q_feat=0.25, q_scaling=2.5e-4, q_offsets=5e-2, steps=None):
+    """GR:77-84 and GR:100-127 over three ``rate_sum`` calls.  ``steps``: the step sizes ``Q [n, 3]`` (columns feat,
+    scaling, offsets) that ``context.context_head`` returned beside ``context``; with it GR:82-84 are not evaluated again
+    (and ``q_*`` are not read).
 
     ``feat [n, feat_dim]``, ``grid_scaling [n, 6]``, ``grid_offsets [n, n_offsets, 3]`` (after the noise of GR:91-97);
     ``context [n, 2 feat_dim + 12 + 6 n_offsets + 3]`` the grid MLP's output (GR:76); ``choose`` bool ``[n]`` (GR:100-101);
@@ -248,9 +250,16 @@ def context_rates(feat, grid_scaling, grid_offsets, context, choose, grid_masks,
     n = context.shape[0]
     mean, scale, mean_scaling, scale_scaling, mean_offsets, scale_offsets, adj_feat, adj_scaling, adj_offsets = \
         torch.split(context, [feat_dim, feat_dim, 6, 6, 3 * n_offsets, 3 * n_offsets, 1, 1, 1], dim=-1)    # GR:77-78
-    Q_feat = q_feat * (1 + torch.tanh(adj_feat))                                                            # GR:82-84
-    Q_scaling = q_scaling * (1 + torch.tanh(adj_scaling))
-    Q_offsets = q_offsets * (1 + torch.tanh(adj_offsets))
+    if steps is None:
+        Q_feat = q_feat * (1 + torch.tanh(adj_feat))                                                        # GR:82-84
+        Q_scaling = q_scaling * (1 + torch.tanh(adj_scaling))
+        Q_offsets = q_offsets * (1 + torch.tanh(adj_offsets))
+    else:
+        if not isinstance(steps, torch.Tensor):
+            raise TypeError(f"{who}: steps must be a torch.Tensor (got {type(steps).__name__})")
+        if tuple(steps.shape) != (n, 3):
+            raise ValueError(f"{who}: steps must be [{n}, 3] (got {list(steps.shape)})")
+        Q_feat, Q_scaling, Q_offsets = steps[:, 0:1], steps[:, 1:2], steps[:, 2:3]
     sum_feat, n_feat = rate_sum(feat, mean, scale, Q_feat, feat_mean, rows=choose)                          # GR:117
     sum_scaling, n_scaling = rate_sum(grid_scaling, mean_scaling, scale_scaling, Q_scaling, scaling_mean, rows=choose)
     sum_offsets, n_offsets_el = rate_sum(grid_offsets.reshape(n, 3 * n_offsets), mean_offsets, scale_offsets, Q_offsets,
