@@ -1,7 +1,8 @@
 """ctypes binding of ``libbloomscene_rast.so`` (C ABI declared in ``include/bloomscene_rast.h``,
 ``include/bloomscene_anchors.h``, ``include/bloomscene_grid.h``, ``include/bloomscene_knn.h``,
 ``include/bloomscene_densify.h``, ``include/bloomscene_entropy.h``, ``include/bloomscene_loss.h``,
-``include/bloomscene_depth_loss.h``, ``include/bloomscene_heads.h`` and ``include/bloomscene_context.h``).
+``include/bloomscene_depth_loss.h``, ``include/bloomscene_heads.h``, ``include/bloomscene_context.h`` and
+``include/bloomscene_anchor_state.h``).
 
 The library is built in-tree (``bloomscene_amd/csrc/Makefile``, hipcc --offload-arch=gfx950).
 There is deliberately NO fallback: if the shared object is missing or a call fails, this module
@@ -136,6 +137,11 @@ SIGNATURES = {
                                   + [_F, C.c_void_p, C.c_void_p, C.c_void_p]),
     "bsr_context_quantise_forward": (C.c_int, [C.c_int] * 5 + [_F, C.c_longlong, C.c_void_p] + [C.c_float] * 3
                                      + [_F, C.c_longlong] * 3 + [_F] * 3 + [_F] + [_F] * 3 + [C.c_void_p]),
+    # include/bloomscene_anchor_state.h
+    "bsr_anchor_visible_forward": (C.c_int, [C.c_int] * 4 + [_F] * 5 + [C.c_longlong] + [_F] * 3 + [_F] * 7 + [C.c_void_p]),
+    "bsr_anchor_visible_backward": (C.c_int, [C.c_int] * 4 + [_F] * 3 + [_F] * 5 + [_F] * 5 + [C.c_void_p]),
+    "bsr_anchor_accumulate_scratch_bytes": (C.c_size_t, [C.c_int] * 2),
+    "bsr_anchor_accumulate": (C.c_int, [C.c_int] * 4 + [_F] * 4 + [C.c_int] + [_F] * 5 + [C.c_void_p, C.c_void_p]),
 }
 
 HeadsPointers = C.c_void_p * 12   # bsr_heads_weights / bsr_heads_weight_grads: (w1, b1, w2, b2) of opacity, cov, color
