@@ -1,8 +1,8 @@
 """ctypes binding of ``libbloomscene_rast.so`` (C ABI declared in ``include/bloomscene_rast.h``,
 ``include/bloomscene_anchors.h``, ``include/bloomscene_grid.h``, ``include/bloomscene_knn.h``,
 ``include/bloomscene_densify.h``, ``include/bloomscene_entropy.h``, ``include/bloomscene_loss.h``,
-``include/bloomscene_depth_loss.h``, ``include/bloomscene_heads.h``, ``include/bloomscene_context.h`` and
-``include/bloomscene_anchor_state.h``).
+``include/bloomscene_depth_loss.h``, ``include/bloomscene_heads.h``, ``include/bloomscene_context.h``,
+``include/bloomscene_anchor_state.h`` and ``include/bloomscene_codec.h``).
 
 The library is built in-tree (``bloomscene_amd/csrc/Makefile``, hipcc --offload-arch=gfx950).
 There is deliberately NO fallback: if the shared object is missing or a call fails, this module
@@ -142,6 +142,16 @@ SIGNATURES = {
     "bsr_anchor_visible_backward": (C.c_int, [C.c_int] * 4 + [_F] * 3 + [_F] * 5 + [_F] * 5 + [C.c_void_p]),
     "bsr_anchor_accumulate_scratch_bytes": (C.c_size_t, [C.c_int] * 2),
     "bsr_anchor_accumulate": (C.c_int, [C.c_int] * 4 + [_F] * 4 + [C.c_int] + [_F] * 5 + [C.c_void_p, C.c_void_p]),
+    # include/bloomscene_codec.h
+    "bsr_codec_stream_bound": (C.c_size_t, [C.c_longlong, C.c_int]),
+    "bsr_codec_scratch_bytes": (C.c_size_t, [C.c_longlong, C.c_int]),
+    "bsr_codec_encode_gaussian": (C.c_int, [C.c_int] * 3 + [_F, C.c_longlong] * 3 + [_F, C.c_int, _F, C.c_float, C.c_int]
+                                  + [_F, C.c_size_t, _F, C.c_void_p, C.c_void_p]),
+    "bsr_codec_decode_gaussian": (C.c_int, [C.c_int] * 3 + [_F, C.c_size_t] + [_F, C.c_longlong] * 2
+                                  + [_F, C.c_int, _F, C.c_float, _F, _F, C.c_void_p]),
+    "bsr_codec_encode_table": (C.c_int, [C.c_int] * 2 + [_F, _F, C.c_longlong, C.c_int, _F, C.c_size_t, _F, C.c_void_p,
+                                                         C.c_void_p]),
+    "bsr_codec_decode_table": (C.c_int, [C.c_int] * 2 + [_F, C.c_size_t, _F, C.c_longlong, _F, _F, C.c_void_p]),
 }
 
 HeadsPointers = C.c_void_p * 12   # bsr_heads_weights / bsr_heads_weight_grads: (w1, b1, w2, b2) of opacity, cov, color
