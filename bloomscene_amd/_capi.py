@@ -1,5 +1,5 @@
 """ctypes binding of ``libbloomscene_rast.so`` (C ABI declared in ``include/bloomscene_rast.h``,
-``include/bloomscene_anchors.h``, ``include/bloomscene_grid.h``, ``include/bloomscene_knn.h``,
+``include/bloomscene_anchors.h``, ``include/bloomscene_grid.h``, ``include/bloomscene_mix_grid.h``, ``include/bloomscene_knn.h``,
 ``include/bloomscene_densify.h``, ``include/bloomscene_entropy.h``, ``include/bloomscene_loss.h``,
 ``include/bloomscene_depth_loss.h``, ``include/bloomscene_heads.h``, ``include/bloomscene_context.h``,
 ``include/bloomscene_anchor_state.h`` and ``include/bloomscene_codec.h``).
@@ -101,6 +101,13 @@ SIGNATURES = {
     "bsr_grid_backward_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "bsr_grid_encode_forward": (C.c_int, [C.c_int] * 5 + [_F] * 6 + [C.c_void_p]),
     "bsr_grid_encode_backward": (C.c_int, [C.c_int] * 5 + [_F] * 7 + [C.c_void_p, C.c_void_p]),
+    # include/bloomscene_mix_grid.h (host arrays of n_grids device pointers / ints: GridPointers, GridInts)
+    "bsr_mix_grid_backward_scratch_bytes": (C.c_size_t, [C.c_int, C.POINTER(C.c_int), C.c_int, C.c_int]),
+    "bsr_mix_grid_forward": (C.c_int, [C.c_int] * 4 + [_F, C.c_longlong, _F, _F] + [C.POINTER(C.c_void_p)] * 3
+                             + [C.POINTER(C.c_int)] * 4 + [_F, _F, C.c_void_p]),
+    "bsr_mix_grid_backward": (C.c_int, [C.c_int] * 4 + [_F, C.c_longlong, _F, C.c_longlong, _F, _F]
+                              + [C.POINTER(C.c_void_p)] * 3 + [C.POINTER(C.c_int)] * 4
+                              + [_F, C.POINTER(C.c_void_p), _F, C.c_void_p, C.c_void_p]),
     # include/bloomscene_knn.h
     "bsr_knn_scratch_bytes": (C.c_size_t, [C.c_int]),
     "bsr_knn_mean_dist": (C.c_int, [C.c_int, _F, _F, C.c_void_p, C.c_void_p]),

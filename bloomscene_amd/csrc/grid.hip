@@ -15,85 +15,13 @@
 //   k_grid_finalize  grad_embeddings = ldexp((float)sum, -s_l) over the whole table (0 outside the levels, NaN where a
 //                    non-finite contribution landed)
 //   k_grid_input_bwd grad_inputs, one thread per (b, d), l-then-ch order
+//
+// The row rule, the cell and the fixed-point scale are in grid_cell.h, shared with mix_grid.hip.
 #include "common.h"
+#include "grid_cell.h"
 #include "../../include/bloomscene_grid.h"
 
 namespace bsr {
-
-#define BSR_GRID_BLOCK 256
-#define BSR_GRID_MAX_LEVELS 64
-
-// GC:44-57: coherent hash (primes of instant-ngp), uint32 wrap-around
-__device__ __forceinline__ uint32_t grid_prime(int d) { return d == 0 ? 1u : (d == 1 ? 2654435761u : 805459861u); }
-
-// GC:62-88 without the feature factor: the row (relative to the level's first row) of grid point p
-template <int D>
-__device__ __forceinline__ uint32_t grid_row(const uint32_t (&p)[D], uint32_t hs, uint32_t res)
-{
-	uint32_t stride = 1, index = 0;
-#pragma unroll
-	for (int d = 0; d < D; d++) {
-		if (stride > hs) break;
-		index += p[d] * stride;
-		stride *= res;
-	}
-	if (stride > hs) {
-		index = 0;
-#pragma unroll
-		for (int d = 0; d < D; d++) index ^= p[d] * grid_prime(d);
-	}
-	return index % hs;
-}
-
-template <int F> struct Feat { float v[F]; };
-
-// One row of F floats: one 8- or 16-byte load per 8 / 16 bytes (embeddings aligned to min(16, 4F): checked on entry)
-template <int F>
-__device__ __forceinline__ Feat<F> load_feat(const float* p)
-{
-	Feat<F> r;
-	if constexpr (F == 1) {
-		r.v[0] = p[0];
-	} else if constexpr (F == 2) {
-		const bsr_f32x2 a = *reinterpret_cast<const bsr_f32x2*>(p);
-		r.v[0] = a.x; r.v[1] = a.y;
-	} else {
-#pragma unroll
-		for (int k = 0; k < F; k += 4) {
-			const bsr_f32x4 a = *reinterpret_cast<const bsr_f32x4*>(p + k);
-			r.v[k] = a.x; r.v[k + 1] = a.y; r.v[k + 2] = a.z; r.v[k + 3] = a.w;
-		}
-	}
-	return r;
-}
-
-template <int F>
-__device__ __forceinline__ void store_feat(float* p, const Feat<F>& r)
-{
-	if constexpr (F == 1) {
-		p[0] = r.v[0];
-	} else if constexpr (F == 2) {
-		bsr_f32x2 a; a.x = r.v[0]; a.y = r.v[1];
-		*reinterpret_cast<bsr_f32x2*>(p) = a;
-	} else {
-#pragma unroll
-		for (int k = 0; k < F; k += 4) {
-			bsr_f32x4 a; a.x = r.v[k]; a.y = r.v[k + 1]; a.z = r.v[k + 2]; a.w = r.v[k + 3];
-			*reinterpret_cast<bsr_f32x4*>(p + k) = a;
-		}
-	}
-}
-
-// The cell of one (point, level) and its 2^D corners: weights, inclusion, rows; wn_re.  GC:166-335.
-template <int D>
-struct Cell {
-	float pos[D];
-	uint32_t pg[D];
-	float w[1 << D];
-	uint32_t row[1 << D];
-	bool ok[1 << D];
-	float wn_re;
-};
 
 // false: the point is outside [0, 1]^D (GC:133-138; NaN counts as outside)
 template <int D>
@@ -106,47 +34,6 @@ __device__ __forceinline__ bool load_point(const float* __restrict__ inputs, lon
 		in = in && (x[d] >= 0.0f && x[d] <= 1.0f);
 	}
 	return in;
-}
-
-template <int D>
-__device__ __forceinline__ void make_cell(const float (&x)[D], uint32_t hs, uint32_t res, long long rows_left, Cell<D>& c)
-{
-	const float scale = (float)(res - 2u);
-#pragma unroll
-	for (int d = 0; d < D; d++) {
-		const float p = x[d] * scale + 0.5f;   // GC:183 (the double 0.5 gives the fp32 sum: p + 0.5 is exact in double)
-		c.pg[d] = (uint32_t)floorf(p);
-		c.pos[d] = p - (float)c.pg[d];
-	}
-	float wn = 0.0f;
-#pragma unroll
-	for (int k = 0; k < (1 << D); k++) {
-		float w = 1.0f;
-		uint32_t p[D];
-		bool ok = true;
-#pragma unroll
-		for (int d = 0; d < D; d++) {
-			if (((k >> d) & 1) == 0) {
-				w *= 1.0f - c.pos[d];
-				p[d] = c.pg[d];
-			} else {
-				w *= c.pos[d];
-				p[d] = min(c.pg[d] + 1u, res - 1u);
-			}
-			ok = ok && p[d] != 0u && p[d] != res - 1u;
-		}
-		// (not in the reference: a level without rows, or a row beyond the table, excludes the corner -- a malformed
-		// offsets table cannot reach outside the caller's buffers)
-		ok = ok && hs != 0u;
-		const uint32_t row = ok ? grid_row<D>(p, hs, res) : 0u;
-		ok = ok && (long long)row < rows_left;
-		c.w[k] = w;
-		c.ok[k] = ok;
-		c.row[k] = row;
-		if (ok) wn += w;
-	}
-	if (wn == 0.0f) wn = 1e-9f;                  // GC:327-329: (float)(0 + 1e-9)
-	c.wn_re = (float)(1.0 / (double)wn);         // GC:330: a double division rounded to fp32 = the fp32 division
 }
 
 template <int D, int F>
@@ -230,17 +117,6 @@ __global__ void __launch_bounds__(BSR_GRID_BLOCK) k_grid_fwd(int N, int L, int n
 
 // ---- backward --------------------------------------------------------------------------------------------------------
 
-// s_l of the header from the level's max |grad| bits (finite values only) and the point count
-__device__ __forceinline__ int grid_scale_exp(uint32_t gbits, int N, int D)
-{
-	if (gbits == 0u) return 0;
-	const uint32_t E = gbits >> 23;
-	const int e = E != 0u ? (int)E - 126 : (32 - __clz((int)(gbits & 0x7fffffu))) - 149;
-	const int k = (N > 1 ? 32 - __clz((int)(N - 1)) : 0) + D;
-	const int s = 61 - k - e;
-	return s < 126 ? s : 126;
-}
-
 // max |grad| of each level over its finite values: blockIdx.y = level, grid-stride over the level's N * F values
 __global__ void __launch_bounds__(BSR_GRID_BLOCK) k_grid_gmax(long long per_level, const uint32_t* __restrict__ grad,
                                                               uint32_t* __restrict__ gmax)
@@ -292,16 +168,8 @@ __global__ void __launch_bounds__(BSR_GRID_BLOCK) k_grid_bwd(int N, int L, int n
 		const float ww = c.w[k] * c.wn_re;
 		const size_t e0 = ((size_t)off + c.row[k]) * F;
 #pragma unroll
-		for (int ch = 0; ch < F; ch++) {
-			const float v = ww * g.v[ch];   // GC:854: w_list[idx] * wn_re * grad_cur[c]
-			const size_t e = e0 + ch;
-			if (__builtin_isfinite(v)) {
-				const long long q = (long long)__builtin_rintf(__builtin_ldexpf(v, s));
-				if (q != 0) atomicAdd(acc + e, (unsigned long long)q);
-			} else {
-				atomicOr(nonfinite + (e >> 5), 1u << (e & 31));
-			}
-		}
+		for (int ch = 0; ch < F; ch++)
+			grid_contribute(ww * g.v[ch], s, e0 + ch, acc, nonfinite);   // GC:854: w_list[idx] * wn_re * grad_cur[c]
 	}
 }
 

@@ -12,7 +12,8 @@ The gradient with respect to ``embeddings`` is summed in 64-bit fixed point with
 every run (the reference's float ``atomicAdd`` is not); the rule and its error bound are in the header.  The gradient
 with respect to ``inputs`` is the reference's ``dy_dx`` formula.  Everything runs on the current torch stream without a
 host synchronisation (capturable into a CUDA graph).  There is no CPU path.  The quantisers BloomScene wraps around the
-table (STE etc.) stay the caller's torch code.
+table (STE etc.) stay the caller's torch code here; ``bloomscene_amd.mix_encoding`` fuses ``STE_binary`` and the four
+tables of ``mix_3D2D_encoding`` into one call.
 """
 from __future__ import annotations
 
