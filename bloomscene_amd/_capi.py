@@ -2,7 +2,7 @@
 ``include/bloomscene_anchors.h``, ``include/bloomscene_grid.h``, ``include/bloomscene_mix_grid.h``, ``include/bloomscene_knn.h``,
 ``include/bloomscene_densify.h``, ``include/bloomscene_entropy.h``, ``include/bloomscene_loss.h``,
 ``include/bloomscene_depth_loss.h``, ``include/bloomscene_heads.h``, ``include/bloomscene_context.h``,
-``include/bloomscene_anchor_state.h`` and ``include/bloomscene_codec.h``).
+``include/bloomscene_anchor_state.h``, ``include/bloomscene_codec.h`` and ``include/bloomscene_adam.h``).
 
 The library is built in-tree (``bloomscene_amd/csrc/Makefile``, hipcc --offload-arch=gfx950).
 There is deliberately NO fallback: if the shared object is missing or a call fails, this module
@@ -31,6 +31,12 @@ OLDER_ABI_ACCEPTED = frozenset({2, 3})
 
 class StageProfile(C.Structure):
     _fields_ = [("name", C.c_char_p), ("total_ms", C.c_double), ("launches", C.c_int)]
+
+
+class AdamTensor(C.Structure):
+    """``bsr_adam_tensor`` of ``include/bloomscene_adam.h``."""
+    _fields_ = [("p", C.c_void_p), ("g", C.c_void_p), ("m", C.c_void_p), ("v", C.c_void_p), ("numel", C.c_longlong),
+                ("lr", C.c_double), ("step", C.c_longlong), ("lr_dev", C.c_void_p), ("step_dev", C.c_void_p)]
 
 
 # name -> (restype, argtypes); every symbol include/*.h declares
@@ -159,6 +165,9 @@ SIGNATURES = {
     "bsr_codec_encode_table": (C.c_int, [C.c_int] * 2 + [_F, _F, C.c_longlong, C.c_int, _F, C.c_size_t, _F, C.c_void_p,
                                                          C.c_void_p]),
     "bsr_codec_decode_table": (C.c_int, [C.c_int] * 2 + [_F, C.c_size_t, _F, C.c_longlong, _F, _F, C.c_void_p]),
+    # include/bloomscene_adam.h (a host array of bsr_adam_tensor: AdamTensor)
+    "bsr_adam_max_tensors": (C.c_int, []),
+    "bsr_adam_step": (C.c_int, [C.c_int, C.POINTER(AdamTensor), C.c_double, C.c_double, C.c_double, C.c_void_p]),
 }
 
 HeadsPointers = C.c_void_p * 12   # bsr_heads_weights / bsr_heads_weight_grads: (w1, b1, w2, b2) of opacity, cov, color
