@@ -2,7 +2,8 @@
 ``include/bloomscene_anchors.h``, ``include/bloomscene_grid.h``, ``include/bloomscene_mix_grid.h``, ``include/bloomscene_knn.h``,
 ``include/bloomscene_densify.h``, ``include/bloomscene_entropy.h``, ``include/bloomscene_loss.h``,
 ``include/bloomscene_depth_loss.h``, ``include/bloomscene_heads.h``, ``include/bloomscene_context.h``,
-``include/bloomscene_anchor_state.h``, ``include/bloomscene_codec.h`` and ``include/bloomscene_adam.h``).
+``include/bloomscene_anchor_state.h``, ``include/bloomscene_codec.h``, ``include/bloomscene_adam.h`` and
+``include/bloomscene_voxelize.h``).
 
 The library is built in-tree (``bloomscene_amd/csrc/Makefile``, hipcc --offload-arch=gfx950).
 There is deliberately NO fallback: if the shared object is missing or a call fails, this module
@@ -168,6 +169,12 @@ SIGNATURES = {
     # include/bloomscene_adam.h (a host array of bsr_adam_tensor: AdamTensor)
     "bsr_adam_max_tensors": (C.c_int, []),
     "bsr_adam_step": (C.c_int, [C.c_int, C.POINTER(AdamTensor), C.c_double, C.c_double, C.c_double, C.c_void_p]),
+    # include/bloomscene_voxelize.h (the source: form, rule, E, P, src, stride, anchor, scaling, stride, K, rows, voxel_size)
+    "bsr_voxel_quantise": (C.c_int, [C.c_int] * 4 + [_F, C.c_longlong, _F, _F, C.c_longlong, C.c_int, _F, C.c_double]
+                           + [_F, _F, C.c_void_p]),
+    "bsr_voxel_unique_scratch_bytes": (C.c_size_t, [C.c_int]),
+    "bsr_voxel_unique": (C.c_int, [C.c_int] * 4 + [_F, C.c_longlong, _F, _F, C.c_longlong, C.c_int, _F, C.c_double]
+                         + [_F] * 7 + [C.c_uint, C.c_void_p]),
 }
 
 HeadsPointers = C.c_void_p * 12   # bsr_heads_weights / bsr_heads_weight_grads: (w1, b1, w2, b2) of opacity, cov, color
