@@ -2,8 +2,8 @@
 ``include/bloomscene_anchors.h``, ``include/bloomscene_grid.h``, ``include/bloomscene_mix_grid.h``, ``include/bloomscene_knn.h``,
 ``include/bloomscene_densify.h``, ``include/bloomscene_entropy.h``, ``include/bloomscene_loss.h``,
 ``include/bloomscene_depth_loss.h``, ``include/bloomscene_heads.h``, ``include/bloomscene_context.h``,
-``include/bloomscene_anchor_state.h``, ``include/bloomscene_codec.h``, ``include/bloomscene_adam.h`` and
-``include/bloomscene_voxelize.h``).
+``include/bloomscene_anchor_state.h``, ``include/bloomscene_codec.h``, ``include/bloomscene_adam.h``,
+``include/bloomscene_voxelize.h`` and ``include/bloomscene_adjust.h``).
 
 The library is built in-tree (``bloomscene_amd/csrc/Makefile``, hipcc --offload-arch=gfx950).
 There is deliberately NO fallback: if the shared object is missing or a call fails, this module
@@ -38,6 +38,13 @@ class AdamTensor(C.Structure):
     """``bsr_adam_tensor`` of ``include/bloomscene_adam.h``."""
     _fields_ = [("p", C.c_void_p), ("g", C.c_void_p), ("m", C.c_void_p), ("v", C.c_void_p), ("numel", C.c_longlong),
                 ("lr", C.c_double), ("step", C.c_longlong), ("lr_dev", C.c_void_p), ("step_dev", C.c_void_p)]
+
+
+class ResizeTensor(C.Structure):
+    """``bsr_resize_tensor`` of ``include/bloomscene_adjust.h``."""
+    _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("append", C.c_void_p), ("flags", C.c_void_p), ("width", C.c_int),
+                ("flags_per_element", C.c_int), ("flag_mask", C.c_uint), ("fill", C.c_uint), ("op", C.c_int),
+                ("clamp_col", C.c_int), ("clamp", C.c_float)]
 
 
 # name -> (restype, argtypes); every symbol include/*.h declares
@@ -175,6 +182,12 @@ SIGNATURES = {
     "bsr_voxel_unique_scratch_bytes": (C.c_size_t, [C.c_int]),
     "bsr_voxel_unique": (C.c_int, [C.c_int] * 4 + [_F, C.c_longlong, _F, _F, C.c_longlong, C.c_int, _F, C.c_double]
                          + [_F] * 7 + [C.c_uint, C.c_void_p]),
+    # include/bloomscene_adjust.h (a host array of L doubles; a host array of bsr_resize_tensor: ResizeTensor)
+    "bsr_adjust_decide_scratch_bytes": (C.c_size_t, [C.c_int]),
+    "bsr_adjust_decide": (C.c_int, [C.c_int, C.c_int] + [_F] * 4 + [C.c_int, C.POINTER(C.c_double)] + [C.c_double] * 3
+                          + [_F] * 4 + [C.c_void_p, C.c_void_p]),
+    "bsr_resize_max_tensors": (C.c_int, []),
+    "bsr_rows_resize": (C.c_int, [C.c_int, C.POINTER(ResizeTensor), C.c_int, C.c_int, C.c_int, _F, C.c_void_p]),
 }
 
 HeadsPointers = C.c_void_p * 12   # bsr_heads_weights / bsr_heads_weight_grads: (w1, b1, w2, b2) of opacity, cov, color
