@@ -1,9 +1,5 @@
-"""ctypes binding of ``libbloomscene_rast.so`` (C ABI declared in ``include/bloomscene_rast.h``,
-``include/bloomscene_anchors.h``, ``include/bloomscene_grid.h``, ``include/bloomscene_mix_grid.h``, ``include/bloomscene_knn.h``,
-``include/bloomscene_densify.h``, ``include/bloomscene_entropy.h``, ``include/bloomscene_loss.h``,
-``include/bloomscene_depth_loss.h``, ``include/bloomscene_heads.h``, ``include/bloomscene_context.h``,
-``include/bloomscene_anchor_state.h``, ``include/bloomscene_codec.h``, ``include/bloomscene_adam.h``,
-``include/bloomscene_voxelize.h`` and ``include/bloomscene_adjust.h``).
+"""ctypes binding of ``libbloomscene_rast.so``: the C ABI the headers under ``include/`` declare (``SIGNATURES`` names
+each).
 
 The library is built in-tree (``bloomscene_amd/csrc/Makefile``, hipcc --offload-arch=gfx950).
 There is deliberately NO fallback: if the shared object is missing or a call fails, this module
@@ -252,6 +248,13 @@ def last_error() -> str:
 def check(rc: int, what: str):
     if rc != 0:
         raise RuntimeError(f"{what} failed: {last_error()}")
+
+
+def call(name: str, *args):
+    """Call the entry point ``name`` (an int status) and raise RuntimeError naming it if the status is not 0."""
+    rc = getattr(lib(), name)(*args)
+    if rc != 0:
+        check(rc, name)
 
 
 def profile_enable(on):

@@ -32,6 +32,7 @@ import struct
 import torch
 
 from . import _capi
+from . import _operands as _ops
 from ._capi import ResizeTensor
 
 __all__ = ["decide", "resize_rows", "quantize_anchor", "grow", "resize_optimizer", "adjust_anchor"]
@@ -48,27 +49,16 @@ SCALING_CLAMP_COL, SCALING_CLAMP = 3, 0.05                                      
 
 
 def _raise_in_order(who, wrong_type, unsupported, wrong_shape, wrong_device):
+    """The first finding, in ``_operands``' order of complaints."""
     for kind, finding in ((TypeError, wrong_type), (NotImplementedError, unsupported), (ValueError, wrong_shape),
                           (ValueError, wrong_device)):
         if finding:
             raise kind(f"{who}: {finding}")
 
 
-def _check_tensors(who, named, dtypes):
-    """-> the first dtype finding (TypeError) of [(name, tensor)]."""
-    for name, t in named:
-        if not isinstance(t, torch.Tensor):
-            return f"{name} must be a torch.Tensor (got {type(t).__name__})"
-        if t.dtype not in dtypes:
-            return f"{name} must be {' or '.join(str(d).replace('torch.', '') for d in dtypes)} (got {t.dtype})"
-    return None
-
-
-def _off_device(named):
-    for name, t in named:
-        if t.device.type != "cuda":
-            return f"{name} must be on the GPU (there is no CPU path)"
-    return None
+def _check_tensors(named, dtypes):
+    """-> the first dtype finding (TypeError) of [(name, tensor)], in ``_operands``' words."""
+    return _ops.wrong_tensor(named, dtypes, half_note=False)
 
 
 # ---- A ----
@@ -87,7 +77,7 @@ def decide(opacity_accum, anchor_demon, offset_gradient_accum, offset_denom, K, 
     who = "decide"
     named = (("opacity_accum", opacity_accum), ("anchor_demon", anchor_demon),
              ("offset_gradient_accum", offset_gradient_accum), ("offset_denom", offset_denom))
-    wrong_type = _check_tensors(who, named, (torch.float32,))
+    wrong_type = _check_tensors(named, (torch.float32,))
     if wrong_type is None and (isinstance(K, bool) or not isinstance(K, int)):
         wrong_type = f"K must be an int (got {type(K).__name__})"
     _raise_in_order(who, wrong_type, None, None, None)
@@ -104,7 +94,7 @@ def decide(opacity_accum, anchor_demon, offset_gradient_accum, offset_denom, K, 
                 wrong_shape = wrong_shape or f"{name} must be [{want}] or [{want}, 1] (got {list(t.shape)})"
         if N * K >= 2 ** 31:
             wrong_shape = wrong_shape or f"need N * K below 2^31 (got {N} * {K})"
-    _raise_in_order(who, None, None, wrong_shape, _off_device(named))
+    _raise_in_order(who, None, None, wrong_shape, _ops.off_gpu(named))
     dev = opacity_accum.device
     stats = [t.detach().reshape(-1).contiguous() for _, t in named]
     offset_flags = torch.empty(N * K, dtype=torch.uint8, device=dev)
@@ -113,15 +103,12 @@ def decide(opacity_accum, anchor_demon, offset_gradient_accum, offset_denom, K, 
     if N == 0:
         return offset_flags, anchor_flags, src_of, torch.zeros(4, dtype=torch.int32, device=dev)
     status = torch.empty(4, dtype=torch.int32, device=dev)
-    lib = _capi.lib()
-    scratch = torch.empty(lib.bsr_adjust_decide_scratch_bytes(N), dtype=torch.uint8, device=dev)
+    scratch = _ops.scratch(_capi.lib().bsr_adjust_decide_scratch_bytes(N), dev)
     thr = (_capi.C.c_double * len(thresholds))(*thresholds)
     ptr = lambda t: t.data_ptr() if t.numel() else None
-    _capi.check(lib.bsr_adjust_decide(N, K, *[ptr(t) for t in stats], len(thresholds), thr,
-                                      check_interval * success_threshold * 0.5, check_interval * success_threshold,
-                                      float(min_opacity), ptr(offset_flags), ptr(anchor_flags), ptr(src_of),
-                                      status.data_ptr(), ptr(scratch), torch.cuda.current_stream(dev).cuda_stream),
-                "bsr_adjust_decide")
+    _capi.call("bsr_adjust_decide", N, K, *[ptr(t) for t in stats], len(thresholds), thr,
+               check_interval * success_threshold * 0.5, check_interval * success_threshold, float(min_opacity),
+               ptr(offset_flags), ptr(anchor_flags), ptr(src_of), status.data_ptr(), ptr(scratch), _ops.stream(dev))
     return offset_flags, anchor_flags, src_of, status
 
 
@@ -159,14 +146,14 @@ def resize_rows(tensors, src_of, n_keep, appends=None, fills=None, ops=None, n_a
     ops = list(ops) if ops is not None else [None] * n
     outs = list(out) if out is not None else [None] * n
     both = (torch.float32, torch.int32)
-    wrong_type = _check_tensors(who, [(f"tensors[{i}]", t) for i, t in enumerate(tensors)], both)
-    wrong_type = wrong_type or _check_tensors(who, [("src_of", src_of)], (torch.int32,))
+    wrong_type = _check_tensors([(f"tensors[{i}]", t) for i, t in enumerate(tensors)], both)
+    wrong_type = wrong_type or _check_tensors([("src_of", src_of)], (torch.int32,))
     flag_tensors = [(f"ops[{i}]: flags", op[1]) for i, op in enumerate(ops) if op is not None and op[0] == "zero_flagged"]
-    wrong_type = wrong_type or _check_tensors(who, flag_tensors, (torch.uint8,))
+    wrong_type = wrong_type or _check_tensors(flag_tensors, (torch.uint8,))
     for i, (t, a, o) in enumerate(zip(tensors, appends, outs)):
         for name, x in ((f"appends[{i}]", a), (f"out[{i}]", o)):
             if x is not None and wrong_type is None:
-                wrong_type = _check_tensors(who, [(name, x)], (t.dtype,)) if isinstance(t, torch.Tensor) else None
+                wrong_type = _check_tensors([(name, x)], (t.dtype,)) if isinstance(t, torch.Tensor) else None
     _raise_in_order(who, wrong_type, None, None, None)
     wrong_shape = None
     if not (len(appends) == len(fills) == len(ops) == len(outs) == n):
@@ -220,7 +207,7 @@ def resize_rows(tensors, src_of, n_keep, appends=None, fills=None, ops=None, n_a
     on_device = [(f"tensors[{i}]", t) for i, t in enumerate(tensors)] + [("src_of", src_of)] + flag_tensors
     on_device += [(f"appends[{i}]", a) for i, a in enumerate(appends) if a is not None]
     on_device += [(f"out[{i}]", o) for i, o in enumerate(outs) if o is not None]
-    _raise_in_order(who, None, None, wrong_shape, _off_device(on_device))
+    _raise_in_order(who, None, None, wrong_shape, _ops.off_gpu(on_device))
     if n == 0:
         return []
     dev = tensors[0].device
@@ -248,8 +235,7 @@ def resize_rows(tensors, src_of, n_keep, appends=None, fills=None, ops=None, n_a
             d.op, d.clamp_col, d.clamp = RESIZE_CLAMP_FROM, int(op[1]), float(op[2])
         results.append(dst)
     src_of = src_of.contiguous()
-    _capi.check(_capi.lib().bsr_rows_resize(n, arr, N, n_keep, A, src_of.data_ptr() if src_of.numel() else None,
-                                            torch.cuda.current_stream(dev).cuda_stream), "bsr_rows_resize")
+    _capi.call("bsr_rows_resize", n, arr, N, n_keep, A, src_of.data_ptr() if src_of.numel() else None, _ops.stream(dev))
     return results
 
 
@@ -278,8 +264,8 @@ def grow(model, offset_flags, rand):
     from . import voxelize as V
     from .densify import scatter_max, voxel_isin
     who = "grow"
-    wrong_type = _check_tensors(who, [("offset_flags", offset_flags)], (torch.uint8,))
-    wrong_type = wrong_type or _check_tensors(who, [(f"rand[{i}]", r) for i, r in enumerate(rand)], (torch.float32,))
+    wrong_type = _check_tensors([("offset_flags", offset_flags)], (torch.uint8,))
+    wrong_type = wrong_type or _check_tensors([(f"rand[{i}]", r) for i, r in enumerate(rand)], (torch.float32,))
     _raise_in_order(who, wrong_type, None, None, None)
     K, depth = int(model.n_offsets), int(model.update_depth)
     N = model._anchor.shape[0]
@@ -291,7 +277,8 @@ def grow(model, offset_flags, rand):
             wrong_shape = wrong_shape or f"rand[{i}] must have {N * K} elements (got {list(r.shape)})"
     if offset_flags.numel() != N * K:
         wrong_shape = wrong_shape or f"offset_flags must have {N * K} elements (got {list(offset_flags.shape)})"
-    _raise_in_order(who, None, None, wrong_shape, _off_device([("offset_flags", offset_flags)] + [("rand", r) for r in rand]))
+    on_device = [("offset_flags", offset_flags)] + [("rand", r) for r in rand]
+    _raise_in_order(who, None, None, wrong_shape, _ops.off_gpu(on_device))
     dev = offset_flags.device
     F = model._anchor_feat.shape[1]
     blocks = {"anchor": [], "scaling": [], "rotation": [], "anchor_feat": []}

@@ -28,34 +28,11 @@ import torch
 from torch.autograd.function import once_differentiable
 
 from . import _capi
+from . import _operands as _ops
+from ._operands import ptr
 
 MAX_F, MAX_K = 64, 16          # BSR_ANCHOR_STATE_MAX_F, BSR_ANCHOR_STATE_MAX_K
 SCAN_BLOCK = 1024              # BSR_ANCHOR_STATE_SCAN
-
-
-def _ptr(t):
-    return None if t is None else t.data_ptr()
-
-
-def _check_dtypes(who, tensors):
-    """tensors: (name, tensor, dtype or tuple of dtypes)."""
-    for name, t, want in tensors:
-        if not isinstance(t, torch.Tensor):
-            raise TypeError(f"{who}: {name} must be a torch.Tensor (got {type(t).__name__})")
-        want = want if isinstance(want, tuple) else (want,)
-        if t.dtype not in want:
-            names = " or ".join(str(w).replace("torch.", "") for w in want)
-            raise TypeError(f"{who}: {name} must be {names} (got {t.dtype})")
-
-
-def _check_devices(who, tensors):
-    for name, t, _ in tensors:
-        if t.device.type != "cuda":
-            raise ValueError(f"{who}: {name} must be on the GPU (there is no CPU path)")
-    first = tensors[0][1].device
-    for name, t, _ in tensors:
-        if t.device != first:
-            raise ValueError(f"{who}: every operand must be on {first} ({name} is on {t.device})")
 
 
 def _check_idx(who, idx, N):
@@ -82,11 +59,9 @@ class _Visible(torch.autograd.Function):
 
         o_anchor, o_feat, o_offsets, o_scaling = new(n, 3), new(n, F), new(n, K, 3), new(n, 6)
         o_masks, o_mask_anchor, o_rate = new(n, K, 1), new(n, dtype=torch.bool), new(())
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        _capi.check(_capi.lib().bsr_anchor_visible_forward(
-            N, n, F, K, _ptr(idx), _ptr(anchor), _ptr(bmin), _ptr(bmax), _ptr(feat), feat.stride(0) if N > 1 else F,
-            _ptr(offset), _ptr(scaling), _ptr(mask), _ptr(o_anchor), _ptr(o_feat), _ptr(o_offsets), _ptr(o_scaling),
-            _ptr(o_masks), _ptr(o_mask_anchor), _ptr(o_rate), stream), "bsr_anchor_visible_forward")
+        _capi.call("bsr_anchor_visible_forward", N, n, F, K, ptr(idx), ptr(anchor), ptr(bmin), ptr(bmax), ptr(feat),
+                   _ops.row_stride(feat, N, F), ptr(offset), ptr(scaling), ptr(mask), ptr(o_anchor), ptr(o_feat),
+                   ptr(o_offsets), ptr(o_scaling), ptr(o_masks), ptr(o_mask_anchor), ptr(o_rate), _ops.stream(dev))
         need = ctx.needs_input_grad
         ctx.save_for_backward(idx, mask if need[7] else None, o_scaling if need[6] else None)
         ctx.sizes = (N, F, K)
@@ -103,21 +78,15 @@ class _Visible(torch.autograd.Function):
         dev = idx.device
         need = ctx.needs_input_grad
 
-        def upstream(g):
-            if g is None:
-                return None
-            return g.contiguous() if g.dtype == torch.float32 else g.float().contiguous()
-
         def dense(wanted, *shape):
             return torch.empty(*shape, dtype=torch.float32, device=dev) if wanted else None
 
-        ups = [upstream(g) for g in (g_anchor, g_feat, g_offsets, g_scaling, g_masks)]
+        ups = [_ops.as_f32_contiguous(g) for g in (g_anchor, g_feat, g_offsets, g_scaling, g_masks)]
         d_anchor, d_feat, d_offset = dense(need[1], N, 3), dense(need[4], N, F), dense(need[5], N, K, 3)
         d_scaling, d_mask = dense(need[6], N, 6), dense(need[7], N, K, 1)
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        _capi.check(_capi.lib().bsr_anchor_visible_backward(
-            N, n, F, K, _ptr(idx), _ptr(mask), _ptr(grid_scaling), *[_ptr(g) for g in ups], _ptr(d_anchor), _ptr(d_feat),
-            _ptr(d_offset), _ptr(d_scaling), _ptr(d_mask), stream), "bsr_anchor_visible_backward")
+        _capi.call("bsr_anchor_visible_backward", N, n, F, K, ptr(idx), ptr(mask), ptr(grid_scaling),
+                   *[ptr(g) for g in ups], ptr(d_anchor), ptr(d_feat), ptr(d_offset), ptr(d_scaling), ptr(d_mask),
+                   _ops.stream(dev))
         return None, d_anchor, None, None, d_feat, d_offset, d_scaling, d_mask
 
 
@@ -133,7 +102,7 @@ def visible(idx, _anchor, x_bound_min, x_bound_max, _anchor_feat, _offset, _scal
     tensors = [("idx", idx, torch.int64), ("_anchor", _anchor, f32), ("x_bound_min", x_bound_min, f32),
                ("x_bound_max", x_bound_max, f32), ("_anchor_feat", _anchor_feat, f32), ("_offset", _offset, f32),
                ("_scaling", _scaling, f32), ("_mask", _mask, f32)]
-    _check_dtypes(who, tensors)
+    _ops.check_tensors(who, tensors, half_note=False)
     if torch.is_grad_enabled():
         for name, t, _ in tensors[2:4]:
             if t.requires_grad:
@@ -163,12 +132,11 @@ def visible(idx, _anchor, x_bound_min, x_bound_max, _anchor_feat, _offset, _scal
             raise ValueError(f"{who}: {name} must hold 3 values (got {list(t.shape)})")
     if idx.numel() > N:
         raise ValueError(f"{who}: idx holds {idx.numel()} rows, more than the {N} anchors")
-    _check_devices(who, tensors)
+    _ops.check_on_gpu(who, tensors)
+    _ops.check_same_device(who, tensors, tensors[0][1].device)
     if check:
         _check_idx(who, idx, N)
-    feat = _anchor_feat
-    if not ((F == 1 or feat.stride(1) == 1) and (N <= 1 or feat.stride(0) >= F)):
-        feat = feat.contiguous()
+    feat = _ops.rows_in_place(_anchor_feat, N, F)
     return _Visible.apply(idx.contiguous(), _anchor.contiguous(), x_bound_min.detach().reshape(3).contiguous(),
                           x_bound_max.detach().reshape(3).contiguous(), feat, _offset.contiguous(), _scaling.contiguous(),
                           _mask.reshape(N, K, 1).contiguous())
@@ -193,7 +161,7 @@ def accumulate(opacity_accum, anchor_demon, offset_gradient_accum, offset_denom,
                ("idx", idx, torch.int64), ("neural_opacity", neural_opacity, f32),
                ("offset_selection_mask", offset_selection_mask, torch.bool), ("radii", radii, (torch.int32, torch.bool)),
                ("viewspace_grad", viewspace_grad, f32)]
-    _check_dtypes(who, tensors)
+    _ops.check_tensors(who, tensors, half_note=False)
     if idx.dim() != 1:
         raise ValueError(f"{who}: idx must be [n] (got {list(idx.shape)})")
     n = idx.numel()
@@ -229,19 +197,17 @@ def accumulate(opacity_accum, anchor_demon, offset_gradient_accum, offset_denom,
     for name, t, _ in tensors[:4]:
         if not t.is_contiguous():
             raise ValueError(f"{who}: {name} is updated in place and must be contiguous")
-    _check_devices(who, tensors)
+    _ops.check_on_gpu(who, tensors)
+    _ops.check_same_device(who, tensors, tensors[0][1].device)
     if check:
         _check_idx(who, idx, N)
     if n == 0:
         return None
     dev = idx.device
-    lib = _capi.lib()
-    scratch = torch.empty(lib.bsr_anchor_accumulate_scratch_bytes(n, K), dtype=torch.uint8, device=dev)
+    scratch = _ops.scratch(_capi.lib().bsr_anchor_accumulate_scratch_bytes(n, K), dev)
     idx, neural_opacity, selection = idx.contiguous(), neural_opacity.contiguous(), offset_selection_mask.contiguous()
     radii, grad = radii.contiguous(), viewspace_grad.contiguous()
-    stream = torch.cuda.current_stream(dev).cuda_stream
-    _capi.check(lib.bsr_anchor_accumulate(
-        N, n, K, M, _ptr(idx), _ptr(neural_opacity), _ptr(selection), _ptr(radii), int(radii.dtype == torch.bool), _ptr(grad),
-        _ptr(opacity_accum), _ptr(anchor_demon), _ptr(offset_gradient_accum), _ptr(offset_denom), _ptr(scratch), stream),
-        "bsr_anchor_accumulate")
+    _capi.call("bsr_anchor_accumulate", N, n, K, M, ptr(idx), ptr(neural_opacity), ptr(selection), ptr(radii),
+               int(radii.dtype == torch.bool), ptr(grad), ptr(opacity_accum), ptr(anchor_demon),
+               ptr(offset_gradient_accum), ptr(offset_denom), ptr(scratch), _ops.stream(dev))
     return None

@@ -25,6 +25,8 @@ import numpy as np
 import torch
 
 from . import _capi
+from . import _operands as _ops
+from ._operands import ptr, row_stride
 
 Q_SINGLE, Q_ROW, Q_ELEMENT = 0, 1, 2          # BSR_CODEC_Q_*
 DEFAULT_STEPS = 256                           # BSR_CODEC_DEFAULT_STEPS
@@ -44,29 +46,13 @@ STATUS = (                                    # BSR_CODEC_BAD_* in bit order
 )
 
 
-def _ptr(t):
-    return None if t is None else t.data_ptr()
-
-
 def _raise_status(who, status):
     if status:
         raise ValueError(f"{who}: " + "; ".join(text for bit, text in enumerate(STATUS) if status >> bit & 1))
 
 
-def _rows_in_place(t, n, C):
-    """``t`` if the kernel can read it where it is (unit column stride, a row stride of at least C), else a dense copy."""
-    if (C == 1 or t.stride(1) == 1) and (n <= 1 or t.stride(0) >= C):
-        return t
-    return t.contiguous()
-
-
-def _row_stride(t, n, C):
-    return t.stride(0) if n > 1 else C
-
-
 class _Gaussian:
-    """The checked operands of one Gaussian call, in the siblings' order: every dtype (TypeError), what is not supported
-    (NotImplementedError), the shapes (ValueError), the devices last."""
+    """The checked operands of one Gaussian call, in ``_operands``' order of complaints (``keep`` may also be bool)."""
 
     def __init__(self, who, x, mean, scale, Q, keep, keep_repeat, scale_min, stream=None):
         named = ([("x", x)] if stream is None else []) + [("mean", mean), ("scale", scale)]
@@ -74,13 +60,11 @@ class _Gaussian:
             named.append(("Q", Q))
         elif not isinstance(Q, (int, float)):
             raise TypeError(f"{who}: Q must be a number or a torch.Tensor (got {type(Q).__name__})")
+        _ops.check_tensors(who, named)
         if keep is not None:
+            if not (isinstance(keep, torch.Tensor) and keep.dtype == torch.bool):   # (a bool mask is taken as it is)
+                _ops.check_tensors(who, [("keep", keep)])
             named.append(("keep", keep))
-        for name, t in named:
-            if not isinstance(t, torch.Tensor):
-                raise TypeError(f"{who}: {name} must be a torch.Tensor (got {type(t).__name__})")
-            if t.dtype != torch.float32 and not (name == "keep" and t.dtype == torch.bool):
-                raise TypeError(f"{who}: {name} must be float32 (got {t.dtype}); half precision is not supported")
         if stream is not None:
             _check_stream(who, stream)
         lead = mean if stream is not None else x
@@ -119,27 +103,22 @@ class _Gaussian:
         if keep is not None:
             if keep.numel() != n * (C // r) or (keep.dim() > 0 and keep.shape[0] != n and n > 0):
                 raise ValueError(f"{who}: keep must be [{n}, {C // r}] (got {list(keep.shape)})")
-        for name, t in named + ([("stream", stream)] if stream is not None else []):
-            if t.device.type != "cuda":
-                raise ValueError(f"{who}: {name} must be on the GPU (there is no CPU path)")
-            if t.device != dev:
-                raise ValueError(f"{who}: every operand must be on {dev} ({name} is on {t.device})")
+        placed = named + ([("stream", stream)] if stream is not None else [])
+        _ops.check_on_gpu(who, placed)
+        _ops.check_same_device(who, placed, dev)
         if q is None:
             q = torch.full((1,), float(Q), dtype=torch.float32, device=dev)
         if keep is not None:
             keep = keep.detach().reshape(n, C // r).to(torch.float32).contiguous()
         self.n, self.C, self.r, self.q, self.keep, self.shape, self.dev = n, C, r, q, keep, shape, dev
         self.scale_min = float(scale_min)
-        two = lambda t: _rows_in_place(t.detach().reshape(n, C), n, C)
+        two = lambda t: _ops.rows_in_place(t.detach().reshape(n, C), n, C)
         self.x = None if stream is not None else two(x)
         self.mean, self.scale = two(mean), two(scale)
 
 
 def _check_stream(who, stream):
-    if not isinstance(stream, torch.Tensor):
-        raise TypeError(f"{who}: stream must be a torch.Tensor (got {type(stream).__name__})")
-    if stream.dtype != torch.uint8:
-        raise TypeError(f"{who}: stream must be uint8 (got {stream.dtype})")
+    _ops.check_tensors(who, [("stream", stream)], torch.uint8)
     if stream.dim() != 1:
         raise ValueError(f"{who}: stream must have one dimension (got {list(stream.shape)})")
 
@@ -164,7 +143,7 @@ def _buffers(who, elements, T, dev):
     if bound == 0:
         raise ValueError(f"{who}: {elements} elements with T = {T} are not supported (the stream could pass 2^32 bytes)")
     stream = torch.empty(bound, dtype=torch.uint8, device=dev)
-    scratch = torch.empty(lib.bsr_codec_scratch_bytes(elements, T), dtype=torch.uint8, device=dev)
+    scratch = _ops.scratch(lib.bsr_codec_scratch_bytes(elements, T), dev)
     result = torch.empty(2, dtype=torch.int32, device=dev)
     return stream, scratch, result
 
@@ -187,10 +166,9 @@ def encode_gaussian(x, mean, scale, Q, keep=None, keep_repeat=1, scale_min=1e-9,
     T = _steps(who, T)
     n, C = op.n, op.C
     stream, scratch, result = _buffers(who, n * C, T, op.dev)
-    _capi.check(_capi.lib().bsr_codec_encode_gaussian(
-        n, C, op.r, _ptr(op.x), _row_stride(op.x, n, C), _ptr(op.mean), _row_stride(op.mean, n, C), _ptr(op.scale),
-        _row_stride(op.scale, n, C), _ptr(op.q), op.q_mode, _ptr(op.keep), op.scale_min, T, _ptr(stream), stream.numel(),
-        _ptr(result), _ptr(scratch), torch.cuda.current_stream(op.dev).cuda_stream), "bsr_codec_encode_gaussian")
+    _capi.call("bsr_codec_encode_gaussian", n, C, op.r, ptr(op.x), row_stride(op.x, n, C), ptr(op.mean),
+               row_stride(op.mean, n, C), ptr(op.scale), row_stride(op.scale, n, C), ptr(op.q), op.q_mode, ptr(op.keep),
+               op.scale_min, T, ptr(stream), stream.numel(), ptr(result), ptr(scratch), _ops.stream(op.dev))
     return _finish_encode(who, stream, result)
 
 
@@ -205,20 +183,16 @@ def decode_gaussian(stream, mean, scale, Q, keep=None, keep_repeat=1, scale_min=
     stream = _aligned(stream)
     out = torch.empty(n, C, dtype=torch.float32, device=op.dev)
     result = torch.empty(2, dtype=torch.int32, device=op.dev)
-    _capi.check(_capi.lib().bsr_codec_decode_gaussian(
-        n, C, op.r, _ptr(stream), stream.numel(), _ptr(op.mean), _row_stride(op.mean, n, C), _ptr(op.scale),
-        _row_stride(op.scale, n, C), _ptr(op.q), op.q_mode, _ptr(op.keep), op.scale_min, _ptr(out), _ptr(result),
-        torch.cuda.current_stream(op.dev).cuda_stream), "bsr_codec_decode_gaussian")
+    _capi.call("bsr_codec_decode_gaussian", n, C, op.r, ptr(stream), stream.numel(), ptr(op.mean),
+               row_stride(op.mean, n, C), ptr(op.scale), row_stride(op.scale, n, C), ptr(op.q), op.q_mode, ptr(op.keep),
+               op.scale_min, ptr(out), ptr(result), _ops.stream(op.dev))
     _raise_status(who, result.tolist()[0] & 0xffffffff)
     return out.reshape(op.shape)
 
 
 def _table(who, cdf, n):
     """-> (cdf as the kernel reads it, L, row stride)."""
-    if not isinstance(cdf, torch.Tensor):
-        raise TypeError(f"{who}: cdf must be a torch.Tensor (got {type(cdf).__name__})")
-    if cdf.dtype != torch.float32:
-        raise TypeError(f"{who}: cdf must be float32 (got {cdf.dtype})")
+    _ops.check_tensors(who, [("cdf", cdf)], half_note=False)
     if cdf.dim() not in (1, 2):
         raise NotImplementedError(f"{who}: a cdf of {cdf.dim()} dimensions is not supported ([L + 1] or [rows, L + 1])")
     L = cdf.shape[-1] - 1
@@ -236,23 +210,16 @@ def encode_symbols(sym, cdf, T=DEFAULT_STEPS):
     """The table model: ``sym`` int16 ``[n]`` in ``[0, L)``, ``cdf`` float32 ``[L + 1]`` (one row for every symbol) or
     ``[n, L + 1]``, each row non-decreasing from 0 to 1.  -> the stream."""
     who = "encode_symbols"
-    if not isinstance(sym, torch.Tensor):
-        raise TypeError(f"{who}: sym must be a torch.Tensor (got {type(sym).__name__})")
-    if sym.dtype != torch.int16:
-        raise TypeError(f"{who}: sym must be int16 (got {sym.dtype})")
+    _ops.check_tensors(who, [("sym", sym)], torch.int16)
     n = sym.numel()
     L, cs = _table(who, cdf, n)
     T = _steps(who, T)
-    for name, t in (("sym", sym), ("cdf", cdf)):
-        if t.device.type != "cuda":
-            raise ValueError(f"{who}: {name} must be on the GPU (there is no CPU path)")
-    if cdf.device != sym.device:
-        raise ValueError(f"{who}: every operand must be on {sym.device} (cdf is on {cdf.device})")
+    _ops.check_on_gpu(who, [("sym", sym), ("cdf", cdf)])
+    _ops.check_same_device(who, [("cdf", cdf)], sym.device)
     sym, cdf = sym.reshape(n).contiguous(), cdf.detach().contiguous()
     stream, scratch, result = _buffers(who, n, T, sym.device)
-    _capi.check(_capi.lib().bsr_codec_encode_table(
-        n, L, _ptr(sym), _ptr(cdf), cs, T, _ptr(stream), stream.numel(), _ptr(result), _ptr(scratch),
-        torch.cuda.current_stream(sym.device).cuda_stream), "bsr_codec_encode_table")
+    _capi.call("bsr_codec_encode_table", n, L, ptr(sym), ptr(cdf), cs, T, ptr(stream), stream.numel(), ptr(result),
+               ptr(scratch), _ops.stream(sym.device))
     return _finish_encode(who, stream, result)
 
 
@@ -261,23 +228,18 @@ def decode_symbols(stream, cdf, n):
     """-> int16 ``[n]``, the symbols ``encode_symbols`` was given, from the same ``cdf``."""
     who = "decode_symbols"
     n = int(n)
-    if not isinstance(cdf, torch.Tensor):
-        raise TypeError(f"{who}: cdf must be a torch.Tensor (got {type(cdf).__name__})")
+    _ops.check_tensors(who, [("cdf", cdf)], None)
     _check_stream(who, stream)
     if n < 0:
         raise ValueError(f"{who}: n must not be negative (got {n})")
     L, cs = _table(who, cdf, n)
-    for name, t in (("stream", stream), ("cdf", cdf)):
-        if t.device.type != "cuda":
-            raise ValueError(f"{who}: {name} must be on the GPU (there is no CPU path)")
-    if cdf.device != stream.device:
-        raise ValueError(f"{who}: every operand must be on {stream.device} (cdf is on {cdf.device})")
+    _ops.check_on_gpu(who, [("stream", stream), ("cdf", cdf)])
+    _ops.check_same_device(who, [("cdf", cdf)], stream.device)
     stream, cdf = _aligned(stream), cdf.detach().contiguous()
     out = torch.empty(n, dtype=torch.int16, device=stream.device)
     result = torch.empty(2, dtype=torch.int32, device=stream.device)
-    _capi.check(_capi.lib().bsr_codec_decode_table(
-        n, L, _ptr(stream), stream.numel(), _ptr(cdf), cs, _ptr(out), _ptr(result),
-        torch.cuda.current_stream(stream.device).cuda_stream), "bsr_codec_decode_table")
+    _capi.call("bsr_codec_decode_table", n, L, ptr(stream), stream.numel(), ptr(cdf), cs, ptr(out), ptr(result),
+               _ops.stream(stream.device))
     _raise_status(who, result.tolist()[0] & 0xffffffff)
     return out
 

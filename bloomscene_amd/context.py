@@ -26,6 +26,8 @@ from torch import nn
 from torch.autograd.function import once_differentiable
 
 from . import _capi
+from . import _operands as _ops
+from ._operands import ptr, row_stride
 
 MAX_D, MAX_H, MAX_F, MAX_K = 128, 128, 64, 16     # BSR_CONTEXT_MAX_*
 Q_DEFAULT = (0.25, 2.5e-4, 5e-2)                  # GR:52-54: feat, scaling, offsets
@@ -38,52 +40,14 @@ def outputs(F, K):
     return 2 * F + 12 + 6 * K + 3
 
 
-def _ptr(t):
-    return None if t is None else t.data_ptr()
-
-
 def _pointers(tensors):
-    return _capi.ContextPointers(*[_ptr(t) for t in tensors])
-
-
-def _check_dtypes(who, tensors):
-    for name, t in tensors:
-        if not isinstance(t, torch.Tensor):
-            raise TypeError(f"{who}: {name} must be a torch.Tensor (got {type(t).__name__})")
-        if t.dtype != torch.float32:
-            raise TypeError(f"{who}: {name} must be float32 (got {t.dtype}); half precision is not supported")
-
-
-def _rows_in_place(t, n, C):
-    """``t`` if the kernel can read it where it is (unit column stride, a row stride of at least C), else a dense copy."""
-    if (C == 1 or t.stride(1) == 1) and (n <= 1 or t.stride(0) >= C):
-        return t
-    return t.contiguous()
-
-
-def _row_stride(t, n, C):
-    return t.stride(0) if n > 1 else C
+    return _capi.ContextPointers(*[ptr(t) for t in tensors])
 
 
 def grid_weights(mlp_grid):
     """The four parameters (W1, b1, W2, b2) of the ``nn.Sequential`` grid MLP, as they are (live).  It must be ``Linear,
     ReLU, Linear`` with biases; anything else raises NotImplementedError naming the layer."""
-    who, name = "context_head", "mlp_grid"
-    if not isinstance(mlp_grid, nn.Sequential):
-        raise NotImplementedError(f"{who}: {name} must be an nn.Sequential (got {type(mlp_grid).__name__})")
-    want = [nn.Linear, nn.ReLU, nn.Linear]
-    layers = list(mlp_grid)
-    for i in range(max(len(want), len(layers))):
-        if i >= len(want):
-            raise NotImplementedError(f"{who}: {name}[{i}] is a {type(layers[i]).__name__}: no layer is supported there")
-        if i >= len(layers):
-            raise NotImplementedError(f"{who}: {name}[{i}] is missing (a {want[i].__name__} is expected)")
-        if type(layers[i]) is not want[i]:
-            raise NotImplementedError(f"{who}: {name}[{i}] is a {type(layers[i]).__name__} (a {want[i].__name__} is expected)")
-    for i in (0, 2):
-        if layers[i].bias is None:
-            raise NotImplementedError(f"{who}: {name}[{i}] has no bias")
-    return [layers[0].weight, layers[0].bias, layers[2].weight, layers[2].bias]
+    return _ops.sequential_weights("context_head", "mlp_grid", mlp_grid)
 
 
 def _steps(q):
@@ -104,12 +68,10 @@ class _Context(torch.autograd.Function):
         outs = [None if x is None else new(n, C) for x, C in zip(xs, widths)]
         maps = new(n, H) if want_maps else None
         if n > 0:
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            strided = [a for x, C in zip(xs, widths) for a in (_ptr(x), 0 if x is None else _row_stride(x, n, C))]
-            _capi.check(_capi.lib().bsr_context_head_forward(
-                n, D, H, F, K, _ptr(enc), _row_stride(enc, n, D), _pointers(weights), *q, *strided,
-                *[_ptr(t) for t in noises], _ptr(context), _ptr(Q), *[_ptr(t) for t in outs], _ptr(maps), stream),
-                "bsr_context_head_forward")
+            strided = [a for x, C in zip(xs, widths) for a in (ptr(x), 0 if x is None else row_stride(x, n, C))]
+            _capi.call("bsr_context_head_forward", n, D, H, F, K, ptr(enc), row_stride(enc, n, D), _pointers(weights),
+                       *q, *strided, *[ptr(t) for t in noises], ptr(context), ptr(Q), *[ptr(t) for t in outs],
+                       ptr(maps), _ops.stream(dev))
         ctx.save_for_backward(enc, noise_feat, noise_scaling, noise_offsets, *weights)
         ctx.shape = (F, K, q)
         ctx.set_materialize_grads(False)
@@ -130,15 +92,10 @@ class _Context(torch.autograd.Function):
         dev = enc.device
         need = ctx.needs_input_grad
 
-        def upstream(g):
-            if g is None:
-                return None
-            return g.contiguous() if g.dtype == torch.float32 else g.float().contiguous()
-
         g_outs = [g_feat, g_scaling, g_offsets]
         d_xs = [g if need[1 + c] else None for c, g in enumerate(g_outs)]        # the gradient to x is the upstream itself
-        g_context, g_Q = upstream(g_context), upstream(g_Q)
-        g_outs = [upstream(g) for g in g_outs]
+        g_context, g_Q = _ops.as_f32_contiguous(g_context), _ops.as_f32_contiguous(g_Q)
+        g_outs = [_ops.as_f32_contiguous(g) for g in g_outs]
         d_enc, d_weights = None, [None] * 4
         if any(g is not None for g in [g_context, g_Q] + g_outs):
             d_enc = torch.empty(n, D, dtype=torch.float32, device=dev) if need[0] else None
@@ -147,22 +104,20 @@ class _Context(torch.autograd.Function):
             sums = any(d is not None for d in d_weights)
             scratch = None
             if sums and n > 0:
-                scratch = torch.empty(_capi.lib().bsr_context_scratch_bytes(n, D, H, F, K), dtype=torch.uint8, device=dev)
+                scratch = _ops.scratch(_capi.lib().bsr_context_scratch_bytes(n, D, H, F, K), dev)
             if (n > 0 and (sums or d_enc is not None)) or sums:
-                stream = torch.cuda.current_stream(dev).cuda_stream
-                _capi.check(_capi.lib().bsr_context_head_backward(
-                    n, D, H, F, K, _ptr(enc), _row_stride(enc, n, D), _pointers(weights), *q, *[_ptr(t) for t in noises],
-                    _ptr(g_context), _ptr(g_Q), *[_ptr(g) for g in g_outs], _ptr(d_enc),
-                    _pointers(d_weights) if sums else None, _ptr(scratch), stream), "bsr_context_head_backward")
+                _capi.call("bsr_context_head_backward", n, D, H, F, K, ptr(enc), row_stride(enc, n, D),
+                           _pointers(weights), *q, *[ptr(t) for t in noises], ptr(g_context), ptr(g_Q),
+                           *[ptr(g) for g in g_outs], ptr(d_enc), _pointers(d_weights) if sums else None, ptr(scratch),
+                           _ops.stream(dev))
         return (d_enc, *d_xs, None, None, None, None, None, None, None, *d_weights)
 
 
 def _checked(who, enc, weights, F, K, xs, noise=None, means=None, q=Q_DEFAULT):
-    """The header's operands from the caller's tensors, in the siblings' order of complaints: dtypes (TypeError), what is not
-    implemented, shapes (ValueError), and the device last (ValueError: there is no CPU path).  ``xs`` = (feat, grid_scaling,
-    grid_offsets), each a tensor or None; ``noise`` (the training form) a 3-tuple beside it or None; ``means`` (the
-    quantiser) the three scalars.  -> enc, weights, xs as [n, C] rows the kernels can read, noises, means, q, the shape
-    grid_offsets came in."""
+    """The header's operands from the caller's tensors, checked in ``_operands``' order of complaints.  ``xs`` = (feat,
+    grid_scaling, grid_offsets), each a tensor or None; ``noise`` (the training form) a 3-tuple beside it or None;
+    ``means`` (the quantiser) the three scalars.  -> enc, weights, xs as [n, C] rows the kernels can read, noises, means,
+    q, the shape grid_offsets came in."""
     weights = list(weights) if isinstance(weights, (list, tuple)) else [weights]
     if noise is None:
         noise = (None, None, None)
@@ -174,7 +129,7 @@ def _checked(who, enc, weights, F, K, xs, noise=None, means=None, q=Q_DEFAULT):
     if means is not None:
         tensors += [(f"{name}_mean", m) for name, m, x in zip(("feat", "scaling", "offsets"), means, xs) if x is not None]
     tensors += list(zip(WEIGHT_NAMES, weights))
-    _check_dtypes(who, tensors)
+    _ops.check_tensors(who, tensors)
     if torch.is_grad_enabled():
         for c, t in enumerate(noise):
             if t is not None and t.requires_grad:
@@ -239,14 +194,10 @@ def _checked(who, enc, weights, F, K, xs, noise=None, means=None, q=Q_DEFAULT):
                 means[c] = None
             elif m.numel() != 1:
                 raise ValueError(f"{who}: {name}_mean must hold one value (got {list(m.shape)})")
-    for name, t in tensors:
-        if t.device.type != "cuda":
-            raise ValueError(f"{who}: {name} must be on the GPU (there is no CPU path)")
-    for name, t in tensors:
-        if t.device != enc.device:
-            raise ValueError(f"{who}: every operand must be on {enc.device} ({name} is on {t.device})")
-    enc = _rows_in_place(enc, n, D)
-    rows = [None if x is None else _rows_in_place(x, n, C) for x, C in zip(rows, (F, 6, 3 * K))]
+    _ops.check_on_gpu(who, tensors)
+    _ops.check_same_device(who, tensors, enc.device)
+    enc = _ops.rows_in_place(enc, n, D)
+    rows = [None if x is None else _ops.rows_in_place(x, n, C) for x, C in zip(rows, (F, 6, 3 * K))]
     weights = [w if w.is_contiguous() else w.contiguous() for w in weights]
     if means is not None:
         means = [None if m is None else m.detach().reshape(1) for m in means]
@@ -274,7 +225,7 @@ def context_head_tensors(enc, weights, F, K, feat=None, grid_scaling=None, grid_
 
 
 def _module_call(who, mlp_grid, tensors):
-    _check_dtypes(who, [(name, t) for name, t in tensors if t is not None])
+    _ops.check_tensors(who, [(name, t) for name, t in tensors if t is not None])
     return grid_weights(mlp_grid)
 
 
@@ -303,11 +254,9 @@ def _quantise(who, enc, weights, F, K, feat, grid_scaling, grid_offsets, means, 
     outs = [None if x is None else torch.empty(n, C, dtype=torch.float32, device=dev) for x, C in zip(xs, widths)]
     Q = torch.empty(n, 3, dtype=torch.float32, device=dev) if want_steps else None
     if n > 0:
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        strided = [a for x, C in zip(xs, widths) for a in (_ptr(x), 0 if x is None else _row_stride(x, n, C))]
-        _capi.check(_capi.lib().bsr_context_quantise_forward(
-            n, D, H, F, K, _ptr(enc), _row_stride(enc, n, D), _pointers(weights), *q, *strided, *[_ptr(m) for m in means],
-            _ptr(Q), *[_ptr(t) for t in outs], stream), "bsr_context_quantise_forward")
+        strided = [a for x, C in zip(xs, widths) for a in (ptr(x), 0 if x is None else row_stride(x, n, C))]
+        _capi.call("bsr_context_quantise_forward", n, D, H, F, K, ptr(enc), row_stride(enc, n, D), _pointers(weights),
+                   *q, *strided, *[ptr(m) for m in means], ptr(Q), *[ptr(t) for t in outs], _ops.stream(dev))
     if outs[2] is not None:
         outs[2] = outs[2].reshape(offsets_shape)
     return (*outs, Q) if want_steps else tuple(outs)

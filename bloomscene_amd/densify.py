@@ -16,20 +16,8 @@ from __future__ import annotations
 import torch
 
 from . import _capi
+from . import _operands as _ops
 from .grid_encoder import check_call
-
-
-def _check_int64(who, tensors):
-    """The int64 twin of check_call's tensor checks, in its order: every dtype (TypeError) before any device
-    (ValueError)."""
-    for name, t in tensors:
-        if not isinstance(t, torch.Tensor):
-            raise TypeError(f"{who}: {name} must be a torch.Tensor (got {type(t).__name__})")
-        if t.dtype != torch.int64:
-            raise TypeError(f"{who}: {name} must be int64 (got {t.dtype})")
-    for name, t in tensors:
-        if t.device.type != "cuda":
-            raise ValueError(f"{who}: {name} must be on the GPU (there is no CPU path)")
 
 
 def scatter_max(src: torch.Tensor, index: torch.Tensor, dim_size: int, row_map: torch.Tensor | None = None):
@@ -40,15 +28,15 @@ def scatter_max(src: torch.Tensor, index: torch.Tensor, dim_size: int, row_map: 
     contribution ``e`` reads ``src[row_map[e]]``.  -> ``out`` float32 and ``argmax`` int64, ``[dim_size, F]`` (or
     ``[dim_size]`` for a 1-D ``src``); ``argmax`` numbers contributions, not source rows."""
     who = "scatter_max"
-    if not isinstance(src, torch.Tensor):
-        raise TypeError(f"{who}: src must be a torch.Tensor (got {type(src).__name__})")
+    _ops.check_tensors(who, [("src", src)], None)
     if src.dim() not in (1, 2):
         raise ValueError(f"{who}: src must be [S] or [S, F] (got {list(src.shape)})")
     one_d = src.dim() == 1
     src = src.detach().contiguous()
-    if src.dtype != torch.float32:
-        raise TypeError(f"{who}: src must be float32 (got {src.dtype})")
-    _check_int64(who, (("index", index),) + (() if row_map is None else (("row_map", row_map),)))
+    _ops.check_tensors(who, [("src", src)], half_note=False)
+    ints = [("index", index)] + ([] if row_map is None else [("row_map", row_map)])
+    _ops.check_tensors(who, ints, torch.int64)       # (every dtype before any device, as in _operands)
+    _ops.check_on_gpu(who, ints)
     check_call(who, 3, 1, float_tensors=(("src", src),))   # off the GPU ValueError
     S, F = src.shape[0], (1 if one_d else src.shape[1])
     G = int(dim_size)
@@ -77,10 +65,8 @@ def scatter_max(src: torch.Tensor, index: torch.Tensor, dim_size: int, row_map: 
                 torch.full(shape, E, dtype=torch.int64, device=src.device))
     out = torch.empty(shape, dtype=torch.float32, device=src.device)
     arg = torch.empty(shape, dtype=torch.int64, device=src.device)
-    stream = torch.cuda.current_stream(src.device).cuda_stream
-    _capi.check(_capi.lib().bsr_scatter_max(E, S, F, G, src.data_ptr(), None if row_map is None else row_map.data_ptr(),
-                                            index.data_ptr(), is0, is1, out.data_ptr(), arg.data_ptr(), stream),
-                "bsr_scatter_max")
+    _capi.call("bsr_scatter_max", E, S, F, G, src.data_ptr(), _ops.ptr(row_map), index.data_ptr(), is0, is1,
+               out.data_ptr(), arg.data_ptr(), _ops.stream(src.device))
     return out, arg
 
 
@@ -89,8 +75,7 @@ def voxel_isin(query: torch.Tensor, keys: torch.Tensor) -> torch.Tensor:
     row of ``keys`` in all three components (``bsr_voxel_isin``).  ``keys`` may repeat rows."""
     who = "voxel_isin"
     for name, t in (("query", query), ("keys", keys)):
-        if not isinstance(t, torch.Tensor):
-            raise TypeError(f"{who}: {name} must be a torch.Tensor (got {type(t).__name__})")
+        _ops.check_tensors(who, [(name, t)], None)
         if t.dim() != 2 or t.shape[1] != 3:
             raise ValueError(f"{who}: {name} must be [n, 3] (got {list(t.shape)})")
     query, keys = query.contiguous(), keys.contiguous()
@@ -98,15 +83,13 @@ def voxel_isin(query: torch.Tensor, keys: torch.Tensor) -> torch.Tensor:
     U, N = query.shape[0], keys.shape[0]
     if U == 0 or N == 0:
         return torch.zeros(U, dtype=torch.bool, device=query.device)
-    lib = _capi.lib()
-    nbytes = lib.bsr_voxel_isin_scratch_bytes(N)
+    nbytes = _capi.lib().bsr_voxel_isin_scratch_bytes(N)
     if nbytes == 0:
         raise ValueError(f"{who}: too many keys ({N})")
     mask = torch.empty(U, dtype=torch.uint8, device=query.device)
-    scratch = torch.empty(nbytes, dtype=torch.uint8, device=query.device)
-    stream = torch.cuda.current_stream(query.device).cuda_stream
-    _capi.check(lib.bsr_voxel_isin(U, N, query.data_ptr(), keys.data_ptr(), mask.data_ptr(), scratch.data_ptr(), stream),
-                "bsr_voxel_isin")
+    scratch = _ops.scratch(nbytes, query.device)
+    _capi.call("bsr_voxel_isin", U, N, query.data_ptr(), keys.data_ptr(), mask.data_ptr(), scratch.data_ptr(),
+               _ops.stream(query.device))
     return mask.view(torch.bool)
 
 

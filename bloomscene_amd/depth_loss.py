@@ -21,6 +21,7 @@ from __future__ import annotations
 import torch
 
 from . import _capi
+from . import _operands as _ops
 
 VALUE, DOMIN, SMOOTH = 1, 2, 4      # BSR_DEPTH_PRIOR_VALUE, _DOMIN, _SMOOTH
 STATS_BYTES = 128                   # BSR_DEPTH_PRIOR_STATS_BYTES
@@ -30,14 +31,9 @@ SPATIAL_SIGMA, COLOR_SIGMA, KERNEL_SIZE = 2.0, 5.0, 5
 
 
 def _check(who, depth, prior, rgb, terms):
-    """The order of loss.py::_check: every dtype (TypeError), then NotImplementedError, then shapes (ValueError), the
-    device (ValueError) last.  ``prior`` / ``rgb`` may be None where the call has none.  -> (H, W)"""
+    """``_operands``' order of complaints.  ``prior`` / ``rgb`` may be None where the call has none.  -> (H, W)"""
     tensors = [(n, t) for n, t in (("render_depth", depth), ("prior_depth", prior), ("rgb", rgb)) if t is not None]
-    for name, t in tensors:
-        if not isinstance(t, torch.Tensor):
-            raise TypeError(f"{who}: {name} must be a torch.Tensor (got {type(t).__name__})")
-        if t.dtype != torch.float32:
-            raise TypeError(f"{who}: {name} must be float32 (got {t.dtype}); half precision is not supported")
+    _ops.check_tensors(who, tensors)
     for name, t in tensors[1:]:
         if t.requires_grad:
             raise NotImplementedError(f"{who}: the gradient to {name} is not implemented (detach it)")
@@ -60,9 +56,7 @@ def _check(who, depth, prior, rgb, terms):
         raise ValueError(f"{who}: the value term needs H and W of at least 2 (got {[H, W]})")
     if H * W >= 2 ** 31:
         raise ValueError(f"{who}: need fewer than 2^31 pixels (got {H * W})")
-    for name, t in tensors:
-        if t.device.type != "cuda":
-            raise ValueError(f"{who}: {name} must be on the GPU (there is no CPU path)")
+    _ops.check_on_gpu(who, tensors)
     for name, t in tensors[1:]:
         if t.device != depth.device:
             raise ValueError(f"{who}: {name} must be on {depth.device} (got {t.device})")
@@ -97,15 +91,12 @@ class _DepthPrior(torch.autograd.Function):
     def forward(ctx, depth, prior, rgb, terms, w, normalise, keep):
         H, W = depth.shape
         dev = depth.device
-        lib = _capi.lib()
         out = torch.empty(4, dtype=torch.float32, device=dev)
         stats = torch.empty(STATS_BYTES // 8, dtype=torch.float64, device=dev)
-        scratch = torch.empty(lib.bsr_depth_prior_scratch_bytes(H, W), dtype=torch.uint8, device=dev)
-        ptr, sy, sx, sc = _rgb_args(rgb)
-        _capi.check(lib.bsr_depth_prior_forward(
-            H, W, depth.data_ptr(), prior.data_ptr(), ptr, sy, sx, sc, terms, w[0], w[1], w[2], int(normalise), None,
-            out.data_ptr(), stats.data_ptr(), scratch.data_ptr(), torch.cuda.current_stream(dev).cuda_stream),
-            "bsr_depth_prior_forward")
+        scratch = _ops.scratch(_capi.lib().bsr_depth_prior_scratch_bytes(H, W), dev)
+        _capi.call("bsr_depth_prior_forward", H, W, depth.data_ptr(), prior.data_ptr(), *_rgb_args(rgb), terms, w[0],
+                   w[1], w[2], int(normalise), None, out.data_ptr(), stats.data_ptr(), scratch.data_ptr(),
+                   _ops.stream(dev))
         if keep:
             ctx.save_for_backward(depth, prior, rgb, stats)
         ctx.call = (terms, w, normalise, keep)
@@ -125,15 +116,12 @@ class _DepthPrior(torch.autograd.Function):
         depth, prior, rgb, stats = ctx.saved_tensors
         H, W = depth.shape
         dev = depth.device
-        lib = _capi.lib()
-        g = (g.float() if g.dtype != torch.float32 else g).contiguous()
+        g = _ops.as_f32_contiguous(g)
         grad = torch.empty_like(depth)
-        scratch = torch.empty(lib.bsr_depth_prior_scratch_bytes(H, W), dtype=torch.uint8, device=dev)
-        ptr, sy, sx, sc = _rgb_args(rgb)
-        _capi.check(lib.bsr_depth_prior_backward(
-            H, W, depth.data_ptr(), prior.data_ptr(), ptr, sy, sx, sc, terms, w[0], w[1], w[2], int(normalise),
-            stats.data_ptr(), g.data_ptr(), grad.data_ptr(), scratch.data_ptr(),
-            torch.cuda.current_stream(dev).cuda_stream), "bsr_depth_prior_backward")
+        scratch = _ops.scratch(_capi.lib().bsr_depth_prior_scratch_bytes(H, W), dev)
+        _capi.call("bsr_depth_prior_backward", H, W, depth.data_ptr(), prior.data_ptr(), *_rgb_args(rgb), terms, w[0],
+                   w[1], w[2], int(normalise), stats.data_ptr(), g.data_ptr(), grad.data_ptr(), scratch.data_ptr(),
+                   _ops.stream(dev))
         return (grad,) + (None,) * 6
 
 
@@ -177,18 +165,16 @@ def depth_prior_maps(render_depth, prior_depth, rgb, normalise=True):
     H, W = _check(who, render_depth, prior_depth, rgb, VALUE | SMOOTH)
     d, p, img = _plane(render_depth), _plane(prior_depth), _image(rgb)
     dev = d.device
-    lib = _capi.lib()
-    stream = torch.cuda.current_stream(dev).cuda_stream
-    ptr, sy, sx, sc = _rgb_args(img)
+    nbytes, stream, rgb_args = _capi.lib().bsr_depth_prior_scratch_bytes(H, W), _ops.stream(dev), _rgb_args(img)
 
     def run(first, second, terms):
         out = torch.empty(4, dtype=torch.float32, device=dev)
         maps = torch.empty((3, H, W), dtype=torch.float32, device=dev)
         stats = torch.empty(STATS_BYTES // 8, dtype=torch.float64, device=dev)
-        scratch = torch.empty(lib.bsr_depth_prior_scratch_bytes(H, W), dtype=torch.uint8, device=dev)
-        _capi.check(lib.bsr_depth_prior_forward(
-            H, W, first.data_ptr(), second.data_ptr(), ptr, sy, sx, sc, terms, 1.0, 1.0, 1.0, int(bool(normalise)),
-            maps.data_ptr(), out.data_ptr(), stats.data_ptr(), scratch.data_ptr(), stream), "bsr_depth_prior_forward")
+        scratch = _ops.scratch(nbytes, dev)
+        _capi.call("bsr_depth_prior_forward", H, W, first.data_ptr(), second.data_ptr(), *rgb_args, terms, 1.0, 1.0,
+                   1.0, int(bool(normalise)), maps.data_ptr(), out.data_ptr(), stats.data_ptr(), scratch.data_ptr(),
+                   stream)
         return maps
 
     m = run(d, p, VALUE | SMOOTH)
@@ -212,11 +198,7 @@ class HuberL1:
 
     def forward(self, pred, gt, rgb):
         who = "HuberL1"
-        for name, t in (("pred", pred), ("gt", gt), ("rgb", rgb)):
-            if not isinstance(t, torch.Tensor):
-                raise TypeError(f"{who}: {name} must be a torch.Tensor (got {type(t).__name__})")
-            if t.dtype != torch.float32:
-                raise TypeError(f"{who}: {name} must be float32 (got {t.dtype}); half precision is not supported")
+        _ops.check_tensors(who, [("pred", pred), ("gt", gt), ("rgb", rgb)])
         if rgb.dim() not in (3, 4) or rgb.shape[-1] != 3:
             raise ValueError(f"{who}: rgb must be [H, W, 3] or [1, H, W, 3] (got {list(rgb.shape)})")
         H, W = rgb.shape[-3:-1]
@@ -236,11 +218,7 @@ class CMD:
 
     def forward(self, x1, x2, n_moments=N_MOMENTS):
         who = "CMD"
-        for name, t in (("x1", x1), ("x2", x2)):
-            if not isinstance(t, torch.Tensor):
-                raise TypeError(f"{who}: {name} must be a torch.Tensor (got {type(t).__name__})")
-            if t.dtype != torch.float32:
-                raise TypeError(f"{who}: {name} must be float32 (got {t.dtype}); half precision is not supported")
+        _ops.check_tensors(who, [("x1", x1), ("x2", x2)])
         if n_moments != N_MOMENTS:
             raise NotImplementedError(f"{who}: only n_moments = {N_MOMENTS} is implemented (got n_moments = {n_moments})")
         if x1.dim() >= 1 and x1.shape[0] != 1 and x1.dim() != 2:
@@ -258,10 +236,7 @@ def bilateral_filter(depth, spatial_sigma=SPATIAL_SIGMA, color_sigma=COLOR_SIGMA
     Only the parameters BloomScene calls it with: ``spatial_sigma = 2``, ``color_sigma = 5`` (NOT the reference's own
     default of 0.1, hence the default here) and ``kernel_size = 5``."""
     who = "bilateral_filter"
-    if not isinstance(depth, torch.Tensor):
-        raise TypeError(f"{who}: depth must be a torch.Tensor (got {type(depth).__name__})")
-    if depth.dtype != torch.float32:
-        raise TypeError(f"{who}: depth must be float32 (got {depth.dtype}); half precision is not supported")
+    _ops.check_tensors(who, [("depth", depth)])
     for name, got, want in (("spatial_sigma", spatial_sigma, SPATIAL_SIGMA), ("color_sigma", color_sigma, COLOR_SIGMA),
                             ("kernel_size", kernel_size, KERNEL_SIZE)):
         if got != want:

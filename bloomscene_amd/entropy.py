@@ -20,40 +20,17 @@ import torch
 from torch import nn
 
 from . import _capi
+from . import _operands as _ops
+from ._operands import ptr, row_stride
 
 Q_SINGLE, Q_ROW, Q_ELEMENT = 0, 1, 2     # BSR_ENTROPY_Q_* of the header
 G_DENSE, G_SINGLE = 0, 1                 # BSR_ENTROPY_G_*
 
 
-def _ptr(t):
-    return None if t is None else t.data_ptr()
-
-
-def _check_float(who, tensors):
-    """grid_encoder.check_call's order: every dtype (TypeError) before any device (ValueError)."""
-    for name, t in tensors:
-        if not isinstance(t, torch.Tensor):
-            raise TypeError(f"{who}: {name} must be a torch.Tensor (got {type(t).__name__})")
-        if t.dtype != torch.float32:
-            raise TypeError(f"{who}: {name} must be float32 (got {t.dtype}); half precision is not supported")
-    for name, t in tensors:
-        if t.device.type != "cuda":
-            raise ValueError(f"{who}: {name} must be on the GPU (there is no CPU path)")
-
-
-def _rows_in_place(t, n, C):
-    """``t`` if the kernel can read it where it is (unit column stride, a row stride of at least C), else a dense copy."""
-    if (C == 1 or t.stride(1) == 1) and (n <= 1 or t.stride(0) >= C):
-        return t
-    return t.contiguous()
-
-
-def _row_stride(t, n, C):
-    return t.stride(0) if n > 1 else C
-
-
 class _Operands:
-    """The checked operands of one call: tensors the kernels can read as they are, and the shape."""
+    """The checked operands of one call: tensors the kernels can read as they are, and the shape.  Every dtype
+    (TypeError) before any device (ValueError); "on the GPU" is checked before the shapes here, "on one device" after
+    them (``_operands`` names this exception to its order)."""
 
     def __init__(self, who, x, mean, scale, Q, x_mean, rows=None, weight=None, weight_repeat=1):
         tensors = [("x", x), ("mean", mean), ("scale", scale)]
@@ -68,13 +45,9 @@ class _Operands:
         if weight is not None:
             tensors.append(("weight", weight))
         if rows is not None:
-            if not isinstance(rows, torch.Tensor):
-                raise TypeError(f"{who}: rows must be a torch.Tensor (got {type(rows).__name__})")
-            if rows.dtype != torch.bool:
-                raise TypeError(f"{who}: rows must be bool (got {rows.dtype})")
-        _check_float(who, tensors)
-        if rows is not None and rows.device.type != "cuda":
-            raise ValueError(f"{who}: rows must be on the GPU (there is no CPU path)")
+            _ops.check_tensors(who, [("rows", rows)], torch.bool)
+        _ops.check_tensors(who, tensors)
+        _ops.check_on_gpu(who, tensors + ([("rows", rows)] if rows is not None else []))
         if x.dim() != 2 or x.shape[1] < 1:
             raise ValueError(f"{who}: x must be [n, C] with C >= 1 (got {list(x.shape)})")
         n, C = x.shape
@@ -121,22 +94,20 @@ class _Operands:
             if t is not None and t.device != dev:
                 raise ValueError(f"{who}: every operand must be on {dev} (got {t.device})")
         self.n, self.C, self.r = n, C, r
-        self.x, self.mean, self.scale = (_rows_in_place(t, n, C) for t in (x, mean, scale))
+        self.x, self.mean, self.scale = (_ops.rows_in_place(t, n, C) for t in (x, mean, scale))
         self.rows, self.weight = rows, weight
 
 
 def _scratch(n, C, r, device):
-    return torch.empty(_capi.lib().bsr_entropy_scratch_bytes(n, C, r), dtype=torch.uint8, device=device)
+    return _ops.scratch(_capi.lib().bsr_entropy_scratch_bytes(n, C, r), device)
 
 
 def _forward(n, C, r, x, mean, scale, q, q_mode, x_mean, rows, weight, bits=None, likelihood=None, total=None, count=None):
     sums = total is not None or count is not None
     scratch = _scratch(n, C, r, x.device) if sums else None
-    stream = torch.cuda.current_stream(x.device).cuda_stream
-    _capi.check(_capi.lib().bsr_entropy_forward(
-        n, C, r, _ptr(x), _row_stride(x, n, C), _ptr(mean), _row_stride(mean, n, C), _ptr(scale), _row_stride(scale, n, C),
-        _ptr(q), q_mode, _ptr(x_mean), _ptr(rows), _ptr(weight), _ptr(bits), _ptr(likelihood), _ptr(total), _ptr(count),
-        _ptr(scratch), stream), "bsr_entropy_forward")
+    _capi.call("bsr_entropy_forward", n, C, r, ptr(x), row_stride(x, n, C), ptr(mean), row_stride(mean, n, C),
+               ptr(scale), row_stride(scale, n, C), ptr(q), q_mode, ptr(x_mean), ptr(rows), ptr(weight), ptr(bits),
+               ptr(likelihood), ptr(total), ptr(count), ptr(scratch), _ops.stream(x.device))
 
 
 def _backward(ctx, g, g_mode):
@@ -153,11 +124,9 @@ def _backward(ctx, g, g_mode):
     dq = out(need[3], *{Q_SINGLE: (1,), Q_ROW: (n,), Q_ELEMENT: (n, C)}[q_mode])
     dw = out(weight is not None and need[6], n, C // r)
     scratch = _scratch(n, C, r, dev) if dq is not None and q_mode == Q_SINGLE else None
-    stream = torch.cuda.current_stream(dev).cuda_stream
-    _capi.check(_capi.lib().bsr_entropy_backward(
-        n, C, r, _ptr(x), _row_stride(x, n, C), _ptr(mean), _row_stride(mean, n, C), _ptr(scale), _row_stride(scale, n, C),
-        _ptr(q), q_mode, _ptr(x_mean), _ptr(rows), _ptr(weight), _ptr(g), g_mode, _ptr(dx), _ptr(dmean), _ptr(dscale),
-        _ptr(dq), _ptr(dw), _ptr(scratch), stream), "bsr_entropy_backward")
+    _capi.call("bsr_entropy_backward", n, C, r, ptr(x), row_stride(x, n, C), ptr(mean), row_stride(mean, n, C),
+               ptr(scale), row_stride(scale, n, C), ptr(q), q_mode, ptr(x_mean), ptr(rows), ptr(weight), ptr(g), g_mode,
+               ptr(dx), ptr(dmean), ptr(dscale), ptr(dq), ptr(dw), ptr(scratch), _ops.stream(dev))
     return dx, dmean, dscale, dq, dw
 
 
@@ -183,10 +152,7 @@ class _Rate(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g, *_):
-        g = g.contiguous()
-        if g.dtype != torch.float32:
-            g = g.float()
-        dx, dmean, dscale, dq, dw = _backward(ctx, g, G_SINGLE if ctx.want_sum else G_DENSE)
+        dx, dmean, dscale, dq, dw = _backward(ctx, _ops.as_f32_contiguous(g), G_SINGLE if ctx.want_sum else G_DENSE)
         return dx, dmean, dscale, dq, None, None, dw, None, None, None
 
 
@@ -255,8 +221,7 @@ def context_rates(feat, grid_scaling, grid_offsets, context, choose, grid_masks,
         Q_scaling = q_scaling * (1 + torch.tanh(adj_scaling))
         Q_offsets = q_offsets * (1 + torch.tanh(adj_offsets))
     else:
-        if not isinstance(steps, torch.Tensor):
-            raise TypeError(f"{who}: steps must be a torch.Tensor (got {type(steps).__name__})")
+        _ops.check_tensors(who, [("steps", steps)], None)
         if tuple(steps.shape) != (n, 3):
             raise ValueError(f"{who}: steps must be [{n}, 3] (got {list(steps.shape)})")
         Q_feat, Q_scaling, Q_offsets = steps[:, 0:1], steps[:, 1:2], steps[:, 2:3]

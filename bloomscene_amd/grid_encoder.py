@@ -22,18 +22,17 @@ import torch
 from torch import nn
 
 from . import _capi
+from . import _operands as _ops
+from ._operands import ptr
 
 SUPPORTED_DIMS = (1, 2, 3)
 SUPPORTED_FEATURES = (1, 2, 4, 8)
 
 
-def _ptr(t):
-    return None if t is None else t.data_ptr()
-
-
 def check_call(who, num_dim, n_features, float_tensors=(), int_tensors=(), binary_vxl=None, min_level_id=None):
-    """The checks every entry point makes before any native call: unsupported reference options raise
-    NotImplementedError, unsupported shapes ValueError, dtypes TypeError, tensors off the GPU ValueError."""
+    """The checks every entry point makes before any native call, in an order of its own (``_operands`` states the
+    wrappers'): unsupported reference options raise NotImplementedError, unsupported shapes ValueError, dtypes
+    TypeError, tensors off the GPU ValueError."""
     if binary_vxl is not None:
         raise NotImplementedError(f"{who}: binary_vxl is not supported (include/bloomscene_grid.h)")
     if min_level_id is not None:
@@ -43,16 +42,15 @@ def check_call(who, num_dim, n_features, float_tensors=(), int_tensors=(), binar
         raise ValueError(f"{who}: num_dim must be one of {SUPPORTED_DIMS} (got {num_dim})")
     if n_features not in SUPPORTED_FEATURES:
         raise ValueError(f"{who}: n_features must be one of {SUPPORTED_FEATURES} (got {n_features})")
-    for name, t in float_tensors:
-        if t is not None and t.dtype != torch.float32:
-            raise TypeError(f"{who}: {name} must be float32 (got {t.dtype}); half precision is not supported")
-    for name, t in int_tensors:
-        if t.dtype != torch.int32:
-            raise TypeError(f"{who}: {name} must be int32 (got {t.dtype})")
+    for tensors, dtype in ((float_tensors, torch.float32), (int_tensors, torch.int32)):
+        for name, t in tensors:
+            if t is not None and t.dtype != dtype:
+                raise TypeError(f"{who}: {_ops.dtype_complaint(name, t, dtype)}")
     for name, t in tuple(float_tensors) + tuple(int_tensors):
-        if t is not None and t.device.type != "cuda":
-            raise ValueError(f"{who}: {name} must be on the GPU (there is no CPU path)")
-        if t is not None and not t.is_contiguous():
+        if t is None:
+            continue
+        _ops.check_on_gpu(who, [(name, t)])
+        if not t.is_contiguous():
             raise ValueError(f"{who}: {name} must be contiguous")
 
 
@@ -60,10 +58,8 @@ def forward_into(inputs, embeddings, offsets, resolutions, outputs, dy_dx, n_lev
     """bsr_grid_encode_forward on tensors already checked: outputs [L, N, F], dy_dx [N, L * D * F] or None."""
     N, D = inputs.shape
     F = embeddings.shape[1]
-    stream = torch.cuda.current_stream(inputs.device).cuda_stream
-    _capi.check(_capi.lib().bsr_grid_encode_forward(N, D, F, n_levels, embeddings.shape[0], _ptr(inputs),
-                                                     _ptr(embeddings), _ptr(offsets), _ptr(resolutions),
-                                                     _ptr(outputs), _ptr(dy_dx), stream), "bsr_grid_encode_forward")
+    _capi.call("bsr_grid_encode_forward", N, D, F, n_levels, embeddings.shape[0], ptr(inputs), ptr(embeddings),
+               ptr(offsets), ptr(resolutions), ptr(outputs), ptr(dy_dx), _ops.stream(inputs.device))
 
 
 def backward_into(grad, inputs, offsets, resolutions, grad_embeddings, dy_dx, grad_inputs, n_levels):
@@ -71,13 +67,10 @@ def backward_into(grad, inputs, offsets, resolutions, grad_embeddings, dy_dx, gr
     scratch comes from torch's allocator."""
     N, D = inputs.shape
     rows, F = grad_embeddings.shape
-    lib = _capi.lib()
-    scratch = torch.empty(lib.bsr_grid_backward_scratch_bytes(rows, F, n_levels), dtype=torch.uint8,
-                          device=inputs.device)
-    stream = torch.cuda.current_stream(inputs.device).cuda_stream
-    _capi.check(lib.bsr_grid_encode_backward(N, D, F, n_levels, rows, _ptr(grad), _ptr(inputs), _ptr(offsets),
-                                             _ptr(resolutions), _ptr(dy_dx), _ptr(grad_embeddings),
-                                             _ptr(grad_inputs), _ptr(scratch), stream), "bsr_grid_encode_backward")
+    scratch = _ops.scratch(_capi.lib().bsr_grid_backward_scratch_bytes(rows, F, n_levels), inputs.device)
+    _capi.call("bsr_grid_encode_backward", N, D, F, n_levels, rows, ptr(grad), ptr(inputs), ptr(offsets),
+               ptr(resolutions), ptr(dy_dx), ptr(grad_embeddings), ptr(grad_inputs), ptr(scratch),
+               _ops.stream(inputs.device))
 
 
 class _GridEncode(torch.autograd.Function):

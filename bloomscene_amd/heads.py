@@ -23,6 +23,8 @@ from torch import nn
 from torch.autograd.function import once_differentiable
 
 from . import _capi
+from . import _operands as _ops
+from ._operands import ptr
 
 MAX_F, MAX_K = 64, 16                  # BSR_HEADS_MAX_F, BSR_HEADS_MAX_K
 HEAD_NAMES = ("mlp_opacity", "mlp_cov", "mlp_color")
@@ -31,20 +33,8 @@ HEAD_LAST = (nn.Tanh, None, nn.Sigmoid)
 WEIGHT_NAMES = tuple(f"{h}.{t}" for h in HEAD_NAMES for t in ("W1", "b1", "W2", "b2"))
 
 
-def _ptr(t):
-    return None if t is None else t.data_ptr()
-
-
 def _pointers(tensors):
-    return _capi.HeadsPointers(*[_ptr(t) for t in tensors])
-
-
-def _check_dtypes(who, tensors):
-    for name, t in tensors:
-        if not isinstance(t, torch.Tensor):
-            raise TypeError(f"{who}: {name} must be a torch.Tensor (got {type(t).__name__})")
-        if t.dtype != torch.float32:
-            raise TypeError(f"{who}: {name} must be float32 (got {t.dtype}); half precision is not supported")
+    return _capi.HeadsPointers(*[ptr(t) for t in tensors])
 
 
 def head_weights(mlp_opacity, mlp_cov, mlp_color):
@@ -53,22 +43,7 @@ def head_weights(mlp_opacity, mlp_cov, mlp_color):
     raises NotImplementedError naming the layer."""
     out = []
     for name, mlp, last in zip(HEAD_NAMES, (mlp_opacity, mlp_cov, mlp_color), HEAD_LAST):
-        if not isinstance(mlp, nn.Sequential):
-            raise NotImplementedError(f"anchor_heads: {name} must be an nn.Sequential (got {type(mlp).__name__})")
-        want = [nn.Linear, nn.ReLU, nn.Linear] + ([last] if last is not None else [])
-        layers = list(mlp)
-        for i in range(max(len(want), len(layers))):
-            if i >= len(want):
-                raise NotImplementedError(f"anchor_heads: {name}[{i}] is a {type(layers[i]).__name__}: no layer is supported there")
-            if i >= len(layers):
-                raise NotImplementedError(f"anchor_heads: {name}[{i}] is missing (a {want[i].__name__} is expected)")
-            if type(layers[i]) is not want[i]:
-                raise NotImplementedError(f"anchor_heads: {name}[{i}] is a {type(layers[i]).__name__} "
-                                          f"(a {want[i].__name__} is expected)")
-        for i in (0, 2):
-            if layers[i].bias is None:
-                raise NotImplementedError(f"anchor_heads: {name}[{i}] has no bias")
-        out += [layers[0].weight, layers[0].bias, layers[2].weight, layers[2].bias]
+        out += _ops.sequential_weights("anchor_heads", name, mlp, last)
     return out
 
 
@@ -84,10 +59,9 @@ class _Heads(torch.autograd.Function):
         scale_rot = torch.empty(n * K, 7, dtype=torch.float32, device=dev)
         maps = torch.empty(n * (3 * F + 11 * K), dtype=torch.float32, device=dev) if want_maps else None
         if n > 0:
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            _capi.check(_capi.lib().bsr_anchor_heads_forward(
-                n, F, K, _ptr(feat), feat.stride(0) if n > 1 else F, _ptr(anchor), _ptr(cam), _ptr(mask), _pointers(weights),
-                _ptr(opacity), _ptr(color), _ptr(scale_rot), _ptr(maps), stream), "bsr_anchor_heads_forward")
+            _capi.call("bsr_anchor_heads_forward", n, F, K, ptr(feat), _ops.row_stride(feat, n, F), ptr(anchor),
+                       ptr(cam), ptr(mask), _pointers(weights), ptr(opacity), ptr(color), ptr(scale_rot), ptr(maps),
+                       _ops.stream(dev))
         ctx.save_for_backward(feat, anchor, cam, mask, color, *weights)
         ctx.K = K
         ctx.set_materialize_grads(False)
@@ -106,12 +80,7 @@ class _Heads(torch.autograd.Function):
         dev = feat.device
         need = ctx.needs_input_grad
 
-        def upstream(g):
-            if g is None:
-                return None
-            return g.contiguous() if g.dtype == torch.float32 else g.float().contiguous()
-
-        g_opacity, g_color, g_scale_rot = upstream(g_opacity), upstream(g_color), upstream(g_scale_rot)
+        g_opacity, g_color, g_scale_rot = (_ops.as_f32_contiguous(g) for g in (g_opacity, g_color, g_scale_rot))
         d_feat = torch.empty(n, F, dtype=torch.float32, device=dev) if need[0] else None
         d_anchor = torch.empty(n, 3, dtype=torch.float32, device=dev) if need[1] else None
         d_mask = torch.empty(n, K, dtype=torch.float32, device=dev) if mask is not None and need[3] else None
@@ -120,19 +89,17 @@ class _Heads(torch.autograd.Function):
         sums = any(d is not None for d in d_weights)
         scratch = None
         if sums and n > 0:
-            scratch = torch.empty(_capi.lib().bsr_anchor_heads_scratch_bytes(n, F, K), dtype=torch.uint8, device=dev)
+            scratch = _ops.scratch(_capi.lib().bsr_anchor_heads_scratch_bytes(n, F, K), dev)
         if n > 0 or sums:
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            _capi.check(_capi.lib().bsr_anchor_heads_backward(
-                n, F, K, _ptr(feat), feat.stride(0) if n > 1 else F, _ptr(anchor), _ptr(cam), _ptr(mask), _pointers(weights),
-                _ptr(color), _ptr(g_opacity), _ptr(g_color), _ptr(g_scale_rot), _ptr(d_feat), _ptr(d_anchor), _ptr(d_mask),
-                _pointers(d_weights) if sums else None, _ptr(scratch), stream), "bsr_anchor_heads_backward")
+            _capi.call("bsr_anchor_heads_backward", n, F, K, ptr(feat), _ops.row_stride(feat, n, F), ptr(anchor),
+                       ptr(cam), ptr(mask), _pointers(weights), ptr(color), ptr(g_opacity), ptr(g_color),
+                       ptr(g_scale_rot), ptr(d_feat), ptr(d_anchor), ptr(d_mask),
+                       _pointers(d_weights) if sums else None, ptr(scratch), _ops.stream(dev))
         return (d_feat, d_anchor, None, d_mask, None, None, *d_weights)
 
 
 def _checked(who, feat, anchor, camera_center, weights, K, offset_mask):
-    """The header's operands from the caller's tensors, in the siblings' order of complaints: dtypes (TypeError), what is not
-    implemented, shapes (ValueError), and the device last (ValueError: there is no CPU path)."""
+    """The header's operands from the caller's tensors, checked in ``_operands``' order of complaints."""
     weights = list(weights)
     if len(weights) != 12:
         raise ValueError(f"{who}: weights must be the twelve tensors {', '.join(WEIGHT_NAMES)} (got {len(weights)})")
@@ -140,7 +107,7 @@ def _checked(who, feat, anchor, camera_center, weights, K, offset_mask):
     if offset_mask is not None:
         tensors.append(("offset_mask", offset_mask))
     tensors += list(zip(WEIGHT_NAMES, weights))
-    _check_dtypes(who, tensors)
+    _ops.check_tensors(who, tensors)
     if camera_center.requires_grad and torch.is_grad_enabled():
         raise NotImplementedError(f"{who}: camera_center requires a gradient; the heads give none to the camera")
     if isinstance(K, bool) or not isinstance(K, int):
@@ -168,14 +135,9 @@ def _checked(who, feat, anchor, camera_center, weights, K, offset_mask):
             if tuple(weights[4 * h + i].shape) != shape:
                 raise ValueError(f"{who}: {WEIGHT_NAMES[4 * h + i]} must be {list(shape)} for F = {F}, K = {K} "
                                  f"(got {list(weights[4 * h + i].shape)})")
-    for name, t in tensors:
-        if t.device.type != "cuda":
-            raise ValueError(f"{who}: {name} must be on the GPU (there is no CPU path)")
-    for name, t in tensors:
-        if t.device != feat.device:
-            raise ValueError(f"{who}: every operand must be on {feat.device} ({name} is on {t.device})")
-    if not ((F == 1 or feat.stride(1) == 1) and (n <= 1 or feat.stride(0) >= F)):
-        feat = feat.contiguous()
+    _ops.check_on_gpu(who, tensors)
+    _ops.check_same_device(who, tensors, feat.device)
+    feat = _ops.rows_in_place(feat, n, F)
     weights = [w if w.is_contiguous() else w.contiguous() for w in weights]
     return feat, anchor.contiguous(), camera_center.detach().reshape(3).contiguous(), offset_mask, weights
 
@@ -197,7 +159,7 @@ def anchor_heads(feat, anchor, camera_center, mlp_opacity, mlp_cov, mlp_color, o
     tensors = [("feat", feat), ("anchor", anchor), ("camera_center", camera_center)]
     if offset_mask is not None:
         tensors.append(("offset_mask", offset_mask))
-    _check_dtypes(who, tensors)
+    _ops.check_tensors(who, tensors)
     weights = head_weights(mlp_opacity, mlp_cov, mlp_color)
     K = int(weights[2].shape[0])
     feat, anchor, cam, mask, weights = _checked(who, feat, anchor, camera_center, weights, K, offset_mask)

@@ -15,6 +15,7 @@ from __future__ import annotations
 import torch
 
 from . import _capi
+from . import _operands as _ops
 from .grid_encoder import check_call
 
 
@@ -22,8 +23,7 @@ def mean_dist3(points: torch.Tensor) -> torch.Tensor:
     """``points`` float32 ``[P, 3]`` on the GPU (any strides: copied to contiguous if needed) -> new float32 ``[P]``
     (``bsr_knn_mean_dist``)."""
     who = "mean_dist3"
-    if not isinstance(points, torch.Tensor):
-        raise TypeError(f"{who}: points must be a torch.Tensor (got {type(points).__name__})")
+    _ops.check_tensors(who, [("points", points)], None)
     if points.dim() != 2 or points.shape[1] != 3:
         raise ValueError(f"{who}: points must be [P, 3] (got {list(points.shape)})")
     points = points.contiguous()
@@ -32,9 +32,7 @@ def mean_dist3(points: torch.Tensor) -> torch.Tensor:
     out = torch.empty(P, dtype=torch.float32, device=points.device)
     if P == 0:
         return out
-    lib = _capi.lib()
-    scratch = torch.empty(lib.bsr_knn_scratch_bytes(P), dtype=torch.uint8, device=points.device)
-    stream = torch.cuda.current_stream(points.device).cuda_stream
-    _capi.check(lib.bsr_knn_mean_dist(P, points.data_ptr(), out.data_ptr(), scratch.data_ptr(), stream),
-                "bsr_knn_mean_dist")
+    scratch = _ops.scratch(_capi.lib().bsr_knn_scratch_bytes(P), points.device)
+    _capi.call("bsr_knn_mean_dist", P, points.data_ptr(), out.data_ptr(), scratch.data_ptr(),
+               _ops.stream(points.device))
     return out

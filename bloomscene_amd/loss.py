@@ -17,18 +17,15 @@ from __future__ import annotations
 import torch
 
 from . import _capi
+from . import _operands as _ops
 
 WINDOW_SIZE = 11     # the only window the kernels implement (gaussian(11, 1.5), the header's constants)
 
 
 def _check(who, first, second, names):
-    """The sibling modules' order: every dtype (TypeError) before anything else, the device (ValueError) last."""
+    """``_operands``' order of complaints."""
     tensors = list(zip(names, (first, second)))
-    for name, t in tensors:
-        if not isinstance(t, torch.Tensor):
-            raise TypeError(f"{who}: {name} must be a torch.Tensor (got {type(t).__name__})")
-        if t.dtype != torch.float32:
-            raise TypeError(f"{who}: {name} must be float32 (got {t.dtype}); half precision is not supported")
+    _ops.check_tensors(who, tensors)
     if second.requires_grad:
         raise NotImplementedError(f"{who}: the gradient to {names[1]} is not implemented (detach it)")
     if first.dim() not in (3, 4):
@@ -40,9 +37,7 @@ def _check(who, first, second, names):
         raise ValueError(f"{who}: H and W must be at least 1 (got {list(first.shape)})")
     if first.numel() >= 2 ** 31:
         raise ValueError(f"{who}: need fewer than 2^31 elements (got {first.numel()})")
-    for name, t in tensors:
-        if t.device.type != "cuda":
-            raise ValueError(f"{who}: {name} must be on the GPU (there is no CPU path)")
+    _ops.check_on_gpu(who, tensors)
     if first.device != second.device:
         raise ValueError(f"{who}: both images must be on {first.device} (got {second.device})")
 
@@ -62,14 +57,11 @@ class _Photometric(torch.autograd.Function):
     def forward(ctx, image, gt, lam, which, keep):
         B, C, H, W = shape = _shape(image)
         dev = image.device
-        lib = _capi.lib()
         out = torch.empty(3, dtype=torch.float32, device=dev)
         partials = torch.empty((3,) + shape, dtype=torch.float32, device=dev) if keep else None
-        scratch = torch.empty(lib.bsr_photometric_scratch_bytes(B, C, H, W), dtype=torch.uint8, device=dev)
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        _capi.check(lib.bsr_photometric_forward(
-            B, C, H, W, image.data_ptr(), gt.data_ptr(), lam, None if partials is None else partials.data_ptr(), None,
-            out.data_ptr(), scratch.data_ptr(), stream), "bsr_photometric_forward")
+        scratch = _ops.scratch(_capi.lib().bsr_photometric_scratch_bytes(B, C, H, W), dev)
+        _capi.call("bsr_photometric_forward", B, C, H, W, image.data_ptr(), gt.data_ptr(), lam, _ops.ptr(partials),
+                   None, out.data_ptr(), scratch.data_ptr(), _ops.stream(dev))
         ctx.save_for_backward(image, gt, partials)
         ctx.call = (shape, lam, which)
         ctx.set_materialize_grads(False)     # (no zeros for the two outputs that carry no gradient)
@@ -86,15 +78,11 @@ class _Photometric(torch.autograd.Function):
         g = gs[which]
         if g is None:
             return None, None, None, None, None
-        if g.dtype != torch.float32:
-            g = g.float()
         # d S = -d loss at lambda = 1 (the header): the sign goes into the upstream scalar
-        g = (-g if which == SSIM else g).contiguous()
+        g = _ops.as_f32_contiguous(-g if which == SSIM else g)
         grad = torch.empty_like(image)
-        stream = torch.cuda.current_stream(image.device).cuda_stream
-        _capi.check(_capi.lib().bsr_photometric_backward(
-            B, C, H, W, image.data_ptr(), gt.data_ptr(), partials.data_ptr(), lam, g.data_ptr(), grad.data_ptr(), stream),
-            "bsr_photometric_backward")
+        _capi.call("bsr_photometric_backward", B, C, H, W, image.data_ptr(), gt.data_ptr(), partials.data_ptr(), lam,
+                   g.data_ptr(), grad.data_ptr(), _ops.stream(image.device))
         return grad, None, None, None, None
 
 
@@ -109,13 +97,11 @@ def ssim_map(image, gt):
     _check("ssim_map", image, gt, ("image", "gt"))
     image, gt = image.contiguous(), gt.contiguous()
     B, C, H, W = _shape(image)
-    lib = _capi.lib()
     out = torch.empty(3, dtype=torch.float32, device=image.device)
     m = torch.empty_like(image)
-    scratch = torch.empty(lib.bsr_photometric_scratch_bytes(B, C, H, W), dtype=torch.uint8, device=image.device)
-    _capi.check(lib.bsr_photometric_forward(
-        B, C, H, W, image.data_ptr(), gt.data_ptr(), 1.0, None, m.data_ptr(), out.data_ptr(), scratch.data_ptr(),
-        torch.cuda.current_stream(image.device).cuda_stream), "bsr_photometric_forward")
+    scratch = _ops.scratch(_capi.lib().bsr_photometric_scratch_bytes(B, C, H, W), image.device)
+    _capi.call("bsr_photometric_forward", B, C, H, W, image.data_ptr(), gt.data_ptr(), 1.0, None, m.data_ptr(),
+               out.data_ptr(), scratch.data_ptr(), _ops.stream(image.device))
     return m
 
 
@@ -132,11 +118,7 @@ def photometric_loss(image, gt, lambda_dssim=0.2, return_terms=False):
 def ssim(img1, img2, window_size=11, size_average=True):
     """``ssim`` of utils/loss.py:103-111 (same signature): the mean of the SSIM map, 0-dim, differentiable in ``img1``.
     The same two kernels with lambda = 1.  Only ``window_size = 11`` and ``size_average = True``."""
-    for name, t in (("img1", img1), ("img2", img2)):   # (dtype before the NotImplementedErrors, like _check)
-        if not isinstance(t, torch.Tensor):
-            raise TypeError(f"ssim: {name} must be a torch.Tensor (got {type(t).__name__})")
-        if t.dtype != torch.float32:
-            raise TypeError(f"ssim: {name} must be float32 (got {t.dtype}); half precision is not supported")
+    _ops.check_tensors("ssim", [("img1", img1), ("img2", img2)])   # (dtypes before the NotImplementedErrors)
     if window_size != WINDOW_SIZE:
         raise NotImplementedError(f"ssim: only window_size = {WINDOW_SIZE} is implemented (got {window_size})")
     if not size_average:

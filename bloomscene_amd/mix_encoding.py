@@ -28,26 +28,13 @@ from torch import nn
 from torch.autograd.function import once_differentiable
 
 from . import _capi
+from . import _operands as _ops
+from ._operands import ptr, row_stride
 from .grid_encoder import SUPPORTED_FEATURES, GridEncoder
 
 MAX_GRIDS = 4      # BSR_MIX_MAX_GRIDS
 MAX_LEVELS = 64    # over all grids
 MIX_DIMS = ((0, 1, 2), (0, 1), (0, 2), (1, 2))   # scene/gaussian_model.py:100-103: xyz, xy, xz, yz
-
-
-def _ptr(t):
-    return None if t is None else t.data_ptr()
-
-
-def _row_stride(t, n, width):
-    return t.stride(0) if n > 1 else width
-
-
-def _rows_in_place(t, n, width):
-    """``t`` if the kernels can read it where it is (unit column stride, a row stride of at least ``width``), else a dense copy."""
-    if (width == 1 or t.stride(1) == 1) and (n <= 1 or t.stride(0) >= width):
-        return t
-    return t.contiguous()
 
 
 class _Grids:
@@ -83,10 +70,8 @@ class _MixEncode(torch.autograd.Function):
         out = torch.empty(n, grids.C, dtype=torch.float32, device=dev)
         dy_dx = torch.empty(n, grids.W, dtype=torch.float32, device=dev) if (need_dx or want_maps) else None
         if n > 0 and grids.C > 0:
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            _capi.check(_capi.lib().bsr_mix_grid_forward(
-                n, grids.G, grids.F, int(binary), _ptr(x), _row_stride(x, n, 3), _ptr(bmin), _ptr(bmax), *grids.args(),
-                _ptr(out), _ptr(dy_dx), stream), "bsr_mix_grid_forward")
+            _capi.call("bsr_mix_grid_forward", n, grids.G, grids.F, int(binary), ptr(x), row_stride(x, n, 3), ptr(bmin),
+                       ptr(bmax), *grids.args(), ptr(out), ptr(dy_dx), _ops.stream(dev))
         ctx.save_for_backward(x, bmin, bmax, dy_dx if need_dx else None, *params)
         ctx.mix = (bool(binary), dims, offsets, resolutions)
         if want_maps:
@@ -106,31 +91,27 @@ class _MixEncode(torch.autograd.Function):
         d_x, d_params = None, [None] * grids.G
         if g_out is not None:
             g = g_out if g_out.dtype == torch.float32 else g_out.float()
-            g = _rows_in_place(g, n, grids.C)
+            g = _ops.rows_in_place(g, n, grids.C)
             want = [bool(need[9 + k]) for k in range(grids.G)]
             new = torch.zeros if (n == 0 or grids.C == 0) else torch.empty
             d_params = [new(p.shape, dtype=torch.float32, device=dev) if w else None for p, w in zip(params, want)]
             if need[0] and dy_dx is not None:
                 d_x = torch.empty(n, 3, dtype=torch.float32, device=dev)
             if n > 0 and grids.C > 0 and (any(want) or d_x is not None):
-                lib = _capi.lib()
                 scratch = None
                 if any(want):
                     rows = (C.c_int * grids.G)(*[r if w else 0 for r, w in zip(grids.rows, want)])
-                    scratch = torch.empty(lib.bsr_mix_grid_backward_scratch_bytes(grids.G, rows, grids.F, grids.total_levels),
-                                          dtype=torch.uint8, device=dev)
-                grads = (C.c_void_p * grids.G)(*[_ptr(t) for t in d_params])
-                stream = torch.cuda.current_stream(dev).cuda_stream
-                _capi.check(lib.bsr_mix_grid_backward(
-                    n, grids.G, grids.F, int(binary), _ptr(g), _row_stride(g, n, grids.C), _ptr(x), _row_stride(x, n, 3),
-                    _ptr(bmin), _ptr(bmax), *grids.args(), _ptr(dy_dx), grads, _ptr(d_x), _ptr(scratch), stream),
-                    "bsr_mix_grid_backward")
+                    scratch = _ops.scratch(_capi.lib().bsr_mix_grid_backward_scratch_bytes(grids.G, rows, grids.F,
+                                                                                           grids.total_levels), dev)
+                grads = (C.c_void_p * grids.G)(*[ptr(t) for t in d_params])
+                _capi.call("bsr_mix_grid_backward", n, grids.G, grids.F, int(binary), ptr(g), row_stride(g, n, grids.C),
+                           ptr(x), row_stride(x, n, 3), ptr(bmin), ptr(bmax), *grids.args(), ptr(dy_dx), grads,
+                           ptr(d_x), ptr(scratch), _ops.stream(dev))
         return (d_x, None, None, None, None, None, None, None, None, *d_params)
 
 
 def _checked(who, x, tables, dims, bound_min, bound_max):
-    """The header's operands from the caller's tensors, in the siblings' order of complaints: dtypes (TypeError), what is not
-    implemented, shapes (ValueError), and the device last (ValueError: there is no CPU path)."""
+    """The header's operands from the caller's tensors, checked in ``_operands``' order of complaints."""
     try:
         tables = [tuple(t) for t in tables]
         dims = tuple(tuple(int(k) for k in d) for d in dims)
@@ -142,15 +123,9 @@ def _checked(who, x, tables, dims, bound_min, bound_max):
     floats = [("x", x)] + [(f"tables[{g}] params", t[0]) for g, t in enumerate(tables)]
     floats += [(name, b) for name, b in (("bound_min", bound_min), ("bound_max", bound_max)) if b is not None]
     ints = [(f"tables[{g}] {name}", t[k]) for g, t in enumerate(tables) for k, name in ((1, "offsets"), (2, "resolutions"))]
-    for name, t in floats + ints:
-        if not isinstance(t, torch.Tensor):
-            raise TypeError(f"{who}: {name} must be a torch.Tensor (got {type(t).__name__})")
-    for name, t in floats:
-        if t.dtype != torch.float32:
-            raise TypeError(f"{who}: {name} must be float32 (got {t.dtype}); half precision is not supported")
-    for name, t in ints:
-        if t.dtype != torch.int32:
-            raise TypeError(f"{who}: {name} must be int32 (got {t.dtype})")
+    _ops.check_tensors(who, floats + ints, None)     # (every operand a tensor before any dtype is looked at)
+    _ops.check_tensors(who, floats)
+    _ops.check_tensors(who, ints, torch.int32)
     if torch.is_grad_enabled():
         for name, b in (("bound_min", bound_min), ("bound_max", bound_max)):
             if b is not None and b.requires_grad:
@@ -182,13 +157,9 @@ def _checked(who, x, tables, dims, bound_min, bound_max):
         raise ValueError(f"{who}: at most {MAX_LEVELS} levels over all tables (got {levels})")
     if x.shape[0] * F * levels >= 2 ** 31:
         raise ValueError(f"{who}: n * F * (levels of all tables) must be below 2^31 (got n = {x.shape[0]})")
-    for name, t in floats + ints:
-        if t.device.type != "cuda":
-            raise ValueError(f"{who}: {name} must be on the GPU (there is no CPU path)")
-    for name, t in floats + ints:
-        if t.device != x.device:
-            raise ValueError(f"{who}: every operand must be on {x.device} ({name} is on {t.device})")
-    x = _rows_in_place(x, x.shape[0], 3)
+    _ops.check_on_gpu(who, floats + ints)
+    _ops.check_same_device(who, floats + ints, x.device)
+    x = _ops.rows_in_place(x, x.shape[0], 3)
     params = [p if p.is_contiguous() else p.contiguous() for p, _, _ in tables]
     offsets = [o.detach().contiguous() for _, o, _ in tables]
     resolutions = [r.detach().contiguous() for _, _, r in tables]

@@ -21,10 +21,8 @@ import ctypes as C
 import torch
 
 from . import _capi
-
-
-def _ptr(t):
-    return None if t is None else t.data_ptr()
+from . import _operands as _ops
+from ._operands import ptr
 
 
 def _need_gpu(*tensors):
@@ -54,19 +52,18 @@ class _ExpandAnchors(torch.autograd.Function):
         dev = anchor.device
         a, gs, go, no, co, sr = (_f32c(t) for t in (anchor, grid_scaling, grid_offsets, neural_opacity, color,
                                                     scale_rot))
-        stream = torch.cuda.current_stream(dev).cuda_stream
+        stream = _ops.stream(dev)
         mask = torch.empty(N * K, dtype=torch.bool, device=dev)
         if N * K == 0:
             S = 0
-            scratch = torch.empty(0, dtype=torch.uint8, device=dev)
+            scratch = _ops.scratch(0, dev)
         else:
             nbytes = lib.bsr_anchor_scratch_bytes(N, K)
             if nbytes == 0:
                 raise RuntimeError("expand_anchors: n_offsets must be in 1..256 and N*K < 2^31")
-            scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+            scratch = _ops.scratch(nbytes, dev)
             count = C.c_int(0)
-            _capi.check(lib.bsr_anchor_select(N, K, _ptr(no), _ptr(mask), _ptr(scratch), C.byref(count), stream),
-                        "bsr_anchor_select")
+            _capi.call("bsr_anchor_select", N, K, ptr(no), ptr(mask), ptr(scratch), C.byref(count), stream)
             S = count.value
         # (the host was blocked on the count: the GPU idles until the expansion is launched, so ONE allocation,
         # carved into the five outputs -- rows of 14 floats would interleave them, the sections keep each contiguous)
@@ -77,9 +74,8 @@ class _ExpandAnchors(torch.autograd.Function):
         scaling = packed[10 * S:13 * S].view(S, 3)
         opacity = packed[13 * S:14 * S].view(S, 1)
         if S:
-            _capi.check(lib.bsr_anchor_expand(N, K, S, _ptr(a), _ptr(gs), _ptr(go), _ptr(no), _ptr(co), _ptr(sr),
-                                              _ptr(scratch), _ptr(xyz), _ptr(color_out), _ptr(opacity), _ptr(scaling),
-                                              _ptr(rot), stream), "bsr_anchor_expand")
+            _capi.call("bsr_anchor_expand", N, K, S, ptr(a), ptr(gs), ptr(go), ptr(no), ptr(co), ptr(sr), ptr(scratch),
+                       ptr(xyz), ptr(color_out), ptr(opacity), ptr(scaling), ptr(rot), stream)
         # the mask is an index output and unused outputs need no zero gradients: without this autograd fills a bool
         # [N*K] zero tensor for the mask's "gradient" on every backward (26 us at 1 M candidates)
         ctx.set_materialize_grads(False)
@@ -94,7 +90,6 @@ class _ExpandAnchors(torch.autograd.Function):
         N, K, S = ctx.dims
         gs, go, no, sr, scratch = ctx.saved_tensors
         dev = gs.device
-        lib = _capi.lib()
 
         def up(g):   # a missing upstream gradient means zeros
             return None if g is None or S == 0 else g.contiguous().float()
@@ -106,11 +101,9 @@ class _ExpandAnchors(torch.autograd.Function):
         d_co = torch.empty(N * K, 3, dtype=torch.float32, device=dev)
         d_sr = torch.empty(N * K, 7, dtype=torch.float32, device=dev)
         if N * K:
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            _capi.check(lib.bsr_anchor_expand_backward(
-                N, K, S, _ptr(gs), _ptr(go), _ptr(no), _ptr(sr), _ptr(scratch), _ptr(g_xyz), _ptr(g_color),
-                _ptr(g_opacity), _ptr(g_scaling), _ptr(g_rot), _ptr(d_anchor), _ptr(d_gs), _ptr(d_go), _ptr(d_no),
-                _ptr(d_co), _ptr(d_sr), stream), "bsr_anchor_expand_backward")
+            _capi.call("bsr_anchor_expand_backward", N, K, S, ptr(gs), ptr(go), ptr(no), ptr(sr), ptr(scratch),
+                       ptr(g_xyz), ptr(g_color), ptr(g_opacity), ptr(g_scaling), ptr(g_rot), ptr(d_anchor), ptr(d_gs),
+                       ptr(d_go), ptr(d_no), ptr(d_co), ptr(d_sr), _ops.stream(dev))
         sh = ctx.shapes
         return (d_anchor.view(sh[0]), d_gs.view(sh[1]), d_go.view(sh[2]), d_no.view(sh[3]), d_co.view(sh[4]),
                 d_sr.view(sh[5]))
@@ -151,12 +144,12 @@ class _NeuralRender(torch.autograd.Function):
                                                     scale_rot))
         bg, view, proj, campos = (_dev_f32(t, n, dev) for t, n in ((rs.bg, "bg"), (rs.viewmatrix, "viewmatrix"),
                                                                     (rs.projmatrix, "projmatrix"), (rs.campos, "campos")))
-        stream = torch.cuda.current_stream(dev).cuda_stream
+        stream = _ops.stream(dev)
         mask = torch.empty(N * K, dtype=torch.bool, device=dev)
         nbytes = lib.bsr_anchor_scratch_bytes(N, K) if N * K else 0
         if N * K and nbytes == 0:
             raise RuntimeError("expand_anchors: n_offsets must be in 1..256 and N*K < 2^31")
-        scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        scratch = _ops.scratch(nbytes, dev)
         out_color = torch.empty((3, H, W), dtype=torch.float32, device=dev)
         out_depth = torch.empty((1, H, W), dtype=torch.float32, device=dev)
         packed_box = []
@@ -176,13 +169,11 @@ class _NeuralRender(torch.autograd.Function):
             flags = int(flags) | 4
         S, R = C.c_int(0), C.c_int(int(capacity) if capacity is not None else 0)
         with torch.cuda.device(dev):
-            rc = lib.bsr_anchor_render_forward(
-                N, K, _ptr(a), _ptr(gs), _ptr(go), _ptr(no), _ptr(co), _ptr(sr), _ptr(mask), _ptr(scratch),
-                gauss_cb, None, geom.callback, None, binning.callback, None, img.callback, None,
-                _ptr(bg), W, H, float(rs.scale_modifier), _ptr(view), _ptr(proj), _ptr(campos), float(rs.tanfovx),
-                float(rs.tanfovy), out_color.data_ptr(), out_depth.data_ptr(), int(bool(rs.debug)), stream,
-                C.byref(S), C.byref(R), int(flags))
-        _capi.check(rc, "bsr_anchor_render_forward")
+            _capi.call("bsr_anchor_render_forward", N, K, ptr(a), ptr(gs), ptr(go), ptr(no), ptr(co), ptr(sr),
+                       ptr(mask), ptr(scratch), gauss_cb, None, geom.callback, None, binning.callback, None,
+                       img.callback, None, ptr(bg), W, H, float(rs.scale_modifier), ptr(view), ptr(proj), ptr(campos),
+                       float(rs.tanfovx), float(rs.tanfovy), out_color.data_ptr(), out_depth.data_ptr(),
+                       int(bool(rs.debug)), stream, C.byref(S), C.byref(R), int(flags))
         S, R = S.value, R.value
         # (the last buffer asked for: the first request may have been a guess made before the count was known)
         packed = packed_box[-1] if packed_box else torch.empty(0, dtype=torch.float32, device=dev)
@@ -213,7 +204,6 @@ class _NeuralRender(torch.autograd.Function):
         gs, go, no, sr, scratch, packed, geom_t, bin_t, img_t = ctx.saved_tensors
         bg, view, proj, campos = ctx.cam
         dev = gs.device
-        lib = _capi.lib()
         if g_image is None:   # only the depth output was used downstream
             g_image = torch.zeros((3, H, W), dtype=torch.float32, device=dev)
         g_image = g_image.contiguous().float()
@@ -232,17 +222,15 @@ class _NeuralRender(torch.autograd.Function):
         d_co = torch.empty(N * K, 3, dtype=torch.float32, device=dev)
         d_sr = torch.empty(N * K, 7, dtype=torch.float32, device=dev)
         if N * K:
-            stream = torch.cuda.current_stream(dev).cuda_stream
             with torch.cuda.device(dev):
-                rc = lib.bsr_anchor_render_backward(
-                    N, K, S, R, _ptr(gs), _ptr(go), _ptr(no), _ptr(sr), _ptr(scratch), _ptr(packed) if S else None,
-                    geom_t.data_ptr() if geom_t.numel() else None, bin_t.data_ptr() if bin_t.numel() else None,
-                    img_t.data_ptr() if img_t.numel() else None, _ptr(bg), W, H, float(rs.scale_modifier), _ptr(view),
-                    _ptr(proj), _ptr(campos), float(rs.tanfovx), float(rs.tanfovy), _ptr(g_image), _ptr(ctx.out_depth),
-                    _ptr(g_depth), _ptr(g_xyz), _ptr(g_rgb), _ptr(g_opacity), _ptr(g_scaling), _ptr(g_rot),
-                    _ptr(grads) if S else None, _ptr(d_anchor), _ptr(d_gs), _ptr(d_go), _ptr(d_no), _ptr(d_co), _ptr(d_sr),
-                    int(bool(rs.debug)), stream, ctx.flags)
-            _capi.check(rc, "bsr_anchor_render_backward")
+                _capi.call("bsr_anchor_render_backward", N, K, S, R, ptr(gs), ptr(go), ptr(no), ptr(sr), ptr(scratch),
+                           ptr(packed) if S else None, geom_t.data_ptr() if geom_t.numel() else None,
+                           bin_t.data_ptr() if bin_t.numel() else None, img_t.data_ptr() if img_t.numel() else None,
+                           ptr(bg), W, H, float(rs.scale_modifier), ptr(view), ptr(proj), ptr(campos),
+                           float(rs.tanfovx), float(rs.tanfovy), ptr(g_image), ptr(ctx.out_depth), ptr(g_depth),
+                           ptr(g_xyz), ptr(g_rgb), ptr(g_opacity), ptr(g_scaling), ptr(g_rot),
+                           ptr(grads) if S else None, ptr(d_anchor), ptr(d_gs), ptr(d_go), ptr(d_no), ptr(d_co),
+                           ptr(d_sr), int(bool(rs.debug)), _ops.stream(dev), ctx.flags)
         # the screen-space gradient, where the reference's consumers look for it (viewspace_points.grad)
         ctx.viewspace.grad = grads[14 * S:17 * S].view(S, 3)
         sh = ctx.shapes

@@ -32,6 +32,7 @@ from __future__ import annotations
 import torch
 
 from . import _capi
+from . import _operands as _ops
 from ._capi import AdamTensor
 
 __all__ = ["Adam"]
@@ -136,8 +137,7 @@ class Adam(torch.optim.Optimizer):
     def _gather(self):
         """-> [(group, p, grad, state or None)] of the parameters that have a gradient.  ONE pass over the live tensors (the
         host's cost of a step is this loop and the next: tools/bench_adam.py prints it); the first finding of each kind is
-        kept and the kinds are raised in the siblings' order -- TypeError, NotImplementedError, ValueError, the device
-        last -- before any state is created."""
+        kept and the kinds are raised in ``_operands``' order of complaints before any state is created."""
         f32, cap, state = torch.float32, self._capturable, self.state
         work, dev = [], None
         wrong_type = unsupported = wrong_layout = wrong_device = None
@@ -228,8 +228,7 @@ class Adam(torch.optim.Optimizer):
                 d.lr, d.step = float(group["lr"]), int(step.item()) + 1
                 d.lr_dev = d.step_dev = None
                 steps.append(step)
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        _capi.check(_capi.lib().bsr_adam_step(n, arr, betas[0], betas[1], eps, stream), "bsr_adam_step")
+        _capi.call("bsr_adam_step", n, arr, betas[0], betas[1], eps, _ops.stream(dev))
         if steps:
             torch._foreach_add_(steps, 1.0)
         return None

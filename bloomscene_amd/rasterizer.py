@@ -16,6 +16,7 @@ import torch
 import torch.nn as nn
 
 from . import _capi
+from ._operands import ptr, stream
 from .numerics import FLAG_EXACT_EXP, FLAG_EXACT_GRAD, numerics, resolve_flags  # noqa: F401  (re-exported)
 
 FLAG_NO_READBACK = 4   # BSR_FLAG_NO_READBACK (include/bloomscene_rast.h)
@@ -53,14 +54,6 @@ def _dev_f32(t: torch.Tensor, name: str, device: torch.device):
     if t.dtype != torch.float32:
         t = t.float()
     return t.contiguous()
-
-
-def _ptr(t):
-    return None if t is None else t.data_ptr()
-
-
-def _stream_handle(device):
-    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
 
 class _Scratch:
@@ -118,11 +111,11 @@ def _rasterize_gaussians_native(bg, means3D, colors, opacity, scales, rotations,
     with torch.cuda.device(dev):
         rc = _capi.lib().bsr_forward_ex(
             geom.callback, None, binning.callback, None, img.callback, None,
-            P, int(degree), int(M), _ptr(t["bg"]), W, H, _ptr(t["means3D"]), _ptr(t["sh"]), _ptr(t["colors"]),
-            _ptr(t["opacity"]), _ptr(t["scales"]), float(scale_modifier), _ptr(t["rotations"]), _ptr(t["cov3D"]),
-            _ptr(t["view"]), _ptr(t["proj"]), _ptr(t["campos"]), float(tan_fovx), float(tan_fovy),
+            P, int(degree), int(M), ptr(t["bg"]), W, H, ptr(t["means3D"]), ptr(t["sh"]), ptr(t["colors"]),
+            ptr(t["opacity"]), ptr(t["scales"]), float(scale_modifier), ptr(t["rotations"]), ptr(t["cov3D"]),
+            ptr(t["view"]), ptr(t["proj"]), ptr(t["campos"]), float(tan_fovx), float(tan_fovy),
             int(bool(prefiltered)), out_color.data_ptr(), out_depth.data_ptr(), radii.data_ptr() if P else None,
-            int(bool(debug)), _stream_handle(dev), C.byref(num_rendered), int(flags))
+            int(bool(debug)), stream(dev), C.byref(num_rendered), int(flags))
     _capi.check(rc, "rasterize_gaussians")
     return num_rendered.value, out_color, out_depth, radii, geom.tensor, binning.tensor, img.tensor
 
@@ -160,11 +153,11 @@ def _rasterize_gaussians_views_native(bg, means3D, colors, opacity, scales, rota
     with torch.cuda.device(dev):
         rc = _capi.lib().bsr_forward_views(
             geom.callback, None, binning.callback, None, img.callback, None,
-            P, int(degree), int(M), int(V), _ptr(t["bg"]), W, H, _ptr(t["means3D"]), _ptr(t["sh"]), _ptr(t["colors"]),
-            _ptr(t["opacity"]), _ptr(t["scales"]), float(scale_modifier), _ptr(t["rotations"]), _ptr(t["cov3D"]),
-            _ptr(view), _ptr(proj), _ptr(campos), float(tan_fovx), float(tan_fovy),
+            P, int(degree), int(M), int(V), ptr(t["bg"]), W, H, ptr(t["means3D"]), ptr(t["sh"]), ptr(t["colors"]),
+            ptr(t["opacity"]), ptr(t["scales"]), float(scale_modifier), ptr(t["rotations"]), ptr(t["cov3D"]),
+            ptr(view), ptr(proj), ptr(campos), float(tan_fovx), float(tan_fovy),
             int(bool(prefiltered)), out_color.data_ptr(), out_depth.data_ptr(), radii.data_ptr() if P and V else None,
-            int(bool(debug)), _stream_handle(dev), C.byref(num_rendered), int(flags))
+            int(bool(debug)), stream(dev), C.byref(num_rendered), int(flags))
     _capi.check(rc, "rasterize_gaussians_views")
     return num_rendered.value, out_color, out_depth, radii
 
@@ -206,18 +199,18 @@ def _rasterize_gaussians_backward_native(bg, means3D, radii, colors, scales, rot
                  sh=_dev_f32(sh, "shs", dev), campos=_dev_f32(campos, "campos", dev),
                  gcol=_dev_f32(dL_dout_color, "dL_dout_color", dev), gdep=_dev_f32(dL_dout_depth, "dL_dout_depth", dev))
         radii_c = radii.contiguous()
-        head = (P, int(degree), int(M), int(R), _ptr(t["bg"]), W, H, _ptr(t["means3D"]), _ptr(t["sh"]),
-                _ptr(t["colors"]), _ptr(t["scales"]), float(scale_modifier), _ptr(t["rotations"]), _ptr(t["cov3D"]),
-                _ptr(t["view"]), _ptr(t["proj"]), _ptr(t["campos"]), float(tan_fovx), float(tan_fovy),
+        head = (P, int(degree), int(M), int(R), ptr(t["bg"]), W, H, ptr(t["means3D"]), ptr(t["sh"]),
+                ptr(t["colors"]), ptr(t["scales"]), float(scale_modifier), ptr(t["rotations"]), ptr(t["cov3D"]),
+                ptr(t["view"]), ptr(t["proj"]), ptr(t["campos"]), float(tan_fovx), float(tan_fovy),
                 radii_c.data_ptr(), geomBuffer.data_ptr(), binningBuffer.data_ptr() if binningBuffer.numel() else None,
                 imageBuffer.data_ptr())
-        tail = (_ptr(t["gcol"]), _ptr(t["gdep"]), dL_dmeans2D.data_ptr(),
-                _ptr(dL_dconic), dL_dopacity.data_ptr(), _ptr(dL_dcolors), dL_dmeans3D.data_ptr(),
-                _ptr(dL_dcov3D), dL_dsh.data_ptr() if M else None, dL_dscales.data_ptr(),
-                dL_drotations.data_ptr(), int(bool(debug)), _stream_handle(dev))
+        tail = (ptr(t["gcol"]), ptr(t["gdep"]), dL_dmeans2D.data_ptr(),
+                ptr(dL_dconic), dL_dopacity.data_ptr(), ptr(dL_dcolors), dL_dmeans3D.data_ptr(),
+                ptr(dL_dcov3D), dL_dsh.data_ptr() if M else None, dL_dscales.data_ptr(),
+                dL_drotations.data_ptr(), int(bool(debug)), stream(dev))
         od = None if out_depth is None else _dev_f32(out_depth, "out_depth", dev)
         with torch.cuda.device(dev):
-            rc = _capi.lib().bsr_backward_ex(*head, _ptr(od), *tail, int(flags))
+            rc = _capi.lib().bsr_backward_ex(*head, ptr(od), *tail, int(flags))
         _capi.check(rc, "rasterize_gaussians_backward")
     return dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations
 
@@ -233,7 +226,7 @@ def _mark_visible_native(means3D, viewmatrix, projmatrix):
         m, v, p = _dev_f32(means3D, "means3D", dev), _dev_f32(viewmatrix, "viewmatrix", dev), _dev_f32(projmatrix, "projmatrix", dev)
         with torch.cuda.device(dev):
             rc = _capi.lib().bsr_mark_visible(P, m.data_ptr(), v.data_ptr(), p.data_ptr(), present.data_ptr(),
-                                              _stream_handle(dev))
+                                              stream(dev))
         _capi.check(rc, "mark_visible")
     return present
 
@@ -254,9 +247,9 @@ def _rasterize_gaussians_filter_native(means3D, scales, rotations, scale_modifie
         v, p = _dev_f32(viewmatrix, "viewmatrix", dev), _dev_f32(projmatrix, "projmatrix", dev)
         with torch.cuda.device(dev):
             rc = _capi.lib().bsr_visible_filter(
-                P, 0, int(image_width), int(image_height), m.data_ptr(), _ptr(s), float(scale_modifier), _ptr(r),
-                _ptr(c), v.data_ptr(), p.data_ptr(), float(tan_fovx), float(tan_fovy), int(bool(prefiltered)),
-                radii.data_ptr(), int(bool(debug)), _stream_handle(dev))
+                P, 0, int(image_width), int(image_height), m.data_ptr(), ptr(s), float(scale_modifier), ptr(r),
+                ptr(c), v.data_ptr(), p.data_ptr(), float(tan_fovx), float(tan_fovy), int(bool(prefiltered)),
+                radii.data_ptr(), int(bool(debug)), stream(dev))
         _capi.check(rc, "rasterize_gaussians_filter")
     return radii
 
@@ -283,9 +276,9 @@ def _rasterize_gaussians_filter_indices_native(means3D, scales, rotations, scale
         scratch = torch.empty(lib.bsr_visible_scratch_bytes(P), dtype=torch.uint8, device=dev)
         with torch.cuda.device(dev):
             rc = lib.bsr_visible_filter_indices(
-                P, 0, int(image_width), int(image_height), m.data_ptr(), _ptr(s), float(scale_modifier), _ptr(r),
-                _ptr(c), v.data_ptr(), p.data_ptr(), float(tan_fovx), float(tan_fovy), int(bool(prefiltered)),
-                radii.data_ptr(), idx.data_ptr(), scratch.data_ptr(), C.byref(n), int(bool(debug)), _stream_handle(dev))
+                P, 0, int(image_width), int(image_height), m.data_ptr(), ptr(s), float(scale_modifier), ptr(r),
+                ptr(c), v.data_ptr(), p.data_ptr(), float(tan_fovx), float(tan_fovy), int(bool(prefiltered)),
+                radii.data_ptr(), idx.data_ptr(), scratch.data_ptr(), C.byref(n), int(bool(debug)), stream(dev))
         _capi.check(rc, "rasterize_gaussians_filter_indices")
     return radii, idx[:n.value].long()
 
@@ -309,9 +302,9 @@ def _rasterize_gaussians_filter_views_native(means3D, scales, rotations, scale_m
         v, p = _dev_f32(viewmatrices, "viewmatrices", dev), _dev_f32(projmatrices, "projmatrices", dev)
         with torch.cuda.device(dev):
             rc = _capi.lib().bsr_visible_filter_views(
-                P, V, int(image_width), int(image_height), m.data_ptr(), _ptr(s), float(scale_modifier), _ptr(r),
-                _ptr(c), v.data_ptr(), p.data_ptr(), float(tan_fovx), float(tan_fovy), radii.data_ptr(),
-                int(bool(debug)), _stream_handle(dev))
+                P, V, int(image_width), int(image_height), m.data_ptr(), ptr(s), float(scale_modifier), ptr(r),
+                ptr(c), v.data_ptr(), p.data_ptr(), float(tan_fovx), float(tan_fovy), radii.data_ptr(),
+                int(bool(debug)), stream(dev))
         _capi.check(rc, "rasterize_gaussians_filter_views")
     return radii
 
@@ -347,10 +340,10 @@ def _rasterize_gaussians_filter_groups_native(means3D, scales, rotations, scale_
                               device=dev) if return_counts else None
         with torch.cuda.device(dev):
             rc = lib.bsr_visible_filter_groups(
-                P, V, int(n_groups), int(image_width), int(image_height), m.data_ptr(), _ptr(s), float(scale_modifier),
-                _ptr(r), _ptr(c), _ptr(v), _ptr(p), float(tan_fovx), float(tan_fovy), gv.data_ptr() if V else None,
-                mask.data_ptr(), counts.data_ptr() if return_counts else None, _ptr(scratch), int(bool(debug)),
-                _stream_handle(dev))
+                P, V, int(n_groups), int(image_width), int(image_height), m.data_ptr(), ptr(s), float(scale_modifier),
+                ptr(r), ptr(c), ptr(v), ptr(p), float(tan_fovx), float(tan_fovy), gv.data_ptr() if V else None,
+                mask.data_ptr(), counts.data_ptr() if return_counts else None, ptr(scratch), int(bool(debug)),
+                stream(dev))
         _capi.check(rc, "rasterize_gaussians_filter_groups")
     return (mask, counts) if return_counts else mask
 
@@ -388,11 +381,11 @@ def _gather_rows_native(tensors, idx, idx_stride=1, rows=None, packed=True, debu
         with torch.cuda.device(dev):
             if packed:
                 rc = _capi.lib().bsr_pack_rows(R, int(tensors[0].shape[0]), n, table, wtab, idx.data_ptr(), idx_stride,
-                                               out.data_ptr(), int(bool(debug)), _stream_handle(dev))
+                                               out.data_ptr(), int(bool(debug)), stream(dev))
             else:
                 rc = _capi.lib().bsr_gather_rows(R, int(tensors[0].shape[0]), n, table, wtab, idx.data_ptr(), idx_stride,
                                                  (C.c_void_p * n)(*[t.data_ptr() for t in out]), int(bool(debug)),
-                                                 _stream_handle(dev))
+                                                 stream(dev))
         _capi.check(rc, "gather_rows")
     return out
 
@@ -408,7 +401,7 @@ def read_counts(image_buffer, image_height, image_width):
     kept, R = C.c_int(0), C.c_int(0)
     dev = image_buffer.device
     with torch.cuda.device(dev):
-        rc = _capi.lib().bsr_read_counts(image_buffer.data_ptr(), int(image_width), int(image_height), _stream_handle(dev),
+        rc = _capi.lib().bsr_read_counts(image_buffer.data_ptr(), int(image_width), int(image_height), stream(dev),
                                          C.byref(kept), C.byref(R))
     _capi.check(rc, "bsr_read_counts")
     return kept.value, R.value

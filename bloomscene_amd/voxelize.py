@@ -21,6 +21,7 @@ import numpy as np
 import torch
 
 from . import _capi
+from . import _operands as _ops
 
 # include/bloomscene_voxelize.h
 FORM_COORDS, FORM_POINTS_F, FORM_POINTS_D, FORM_COMPOSITE = 0, 1, 2, 3
@@ -30,19 +31,14 @@ FLAG_TEST_SMALL_CHUNK = 0x100
 
 
 def _check_source(who, x, rows, rule, want_coords, before_device=None):
-    """The checks before any native call, in the siblings' order: dtypes (TypeError), unsupported combinations
-    (NotImplementedError), shapes and values (ValueError; ``before_device`` checks the caller's), devices last
-    (ValueError: there is no CPU path).  -> the form."""
-    if not isinstance(x, torch.Tensor):
-        raise TypeError(f"{who}: the input must be a torch.Tensor (got {type(x).__name__})")
+    """The checks before any native call, in ``_operands``' order of complaints (``before_device`` makes the caller's
+    shape and value checks).  -> the form."""
+    _ops.check_tensors(who, [("the input", x)], None)
     allowed = (torch.float32, torch.float64, torch.int32) if want_coords else (torch.float32, torch.float64)
     if x.dtype not in allowed:
         raise TypeError(f"{who}: the input must be float32, float64{' or int32' if want_coords else ''} (got {x.dtype})")
     if rows is not None:
-        if not isinstance(rows, torch.Tensor):
-            raise TypeError(f"{who}: rows must be a torch.Tensor (got {type(rows).__name__})")
-        if rows.dtype != torch.int64:
-            raise TypeError(f"{who}: rows must be int64 (got {rows.dtype})")
+        _ops.check_tensors(who, [("rows", rows)], torch.int64)
     if rule not in RULES:
         raise ValueError(f"{who}: rule must be 'divide' or 'reciprocal' (got {rule!r})")
     if rule == "reciprocal" and x.dtype == torch.float64:
@@ -58,9 +54,7 @@ def _check_source(who, x, rows, rule, want_coords, before_device=None):
         raise ValueError(f"{who}: need fewer than 2^31 rows")
     if before_device is not None:
         before_device()
-    for name, t in (("the input", x), ("rows", rows)):
-        if t is not None and t.device.type != "cuda":
-            raise ValueError(f"{who}: {name} must be on the GPU (there is no CPU path)")
+    _ops.check_on_gpu(who, [("the input", x)] + ([("rows", rows)] if rows is not None else []))
     return {torch.int32: FORM_COORDS, torch.float32: FORM_POINTS_F, torch.float64: FORM_POINTS_D}[x.dtype]
 
 
@@ -75,7 +69,7 @@ def _strided_rows(x):
     """A [P, 3] tensor the kernels can read in place (unit column stride, a row stride of at least 3), else a copy."""
     if x.shape[0] > 0 and (x.stride(1) != 1 or x.stride(0) < 3):
         x = x.contiguous()
-    return x, (x.stride(0) if x.shape[0] > 1 else 3)
+    return x, _ops.row_stride(x, x.shape[0], 3)
 
 
 class _Source:
@@ -89,7 +83,7 @@ class _Source:
         self.point_dtype = torch.float64 if form == FORM_POINTS_D else torch.float32
 
     def args(self, rule, voxel_size):
-        ptr = lambda t: None if t is None else t.data_ptr()
+        ptr = _ops.ptr
         return (self.form, RULES[rule], self.E, self.P, ptr(self.src), self.stride, ptr(self.anchor), ptr(self.scaling),
                 self.scaling_stride, self.K, ptr(self.rows), float(voxel_size))
 
@@ -111,9 +105,7 @@ def _point_source(who, x, rows, rule, want_coords, voxel_size, size_optional=Fal
 def _quantise(src, voxel_size, rule):
     q = torch.empty(src.E, 3, dtype=torch.int32, device=src.device)
     if src.E:
-        stream = torch.cuda.current_stream(src.device).cuda_stream
-        _capi.check(_capi.lib().bsr_voxel_quantise(*src.args(rule, voxel_size), q.data_ptr(), None, stream),
-                    "bsr_voxel_quantise")
+        _capi.call("bsr_voxel_quantise", *src.args(rule, voxel_size), q.data_ptr(), None, _ops.stream(src.device))
     return q
 
 
@@ -127,17 +119,14 @@ def _unique(who, src, voxel_size, rule, return_points, flags=0):
     points = torch.empty(E, 3, dtype=src.point_dtype, device=dev) if return_points else None
     U = 0
     if E:
-        lib = _capi.lib()
-        nbytes = lib.bsr_voxel_unique_scratch_bytes(E)
+        nbytes = _capi.lib().bsr_voxel_unique_scratch_bytes(E)
         if nbytes == 0:
             raise ValueError(f"{who}: too many rows ({E})")
         status = torch.empty(8, dtype=torch.int32, device=dev)
-        scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        _capi.check(lib.bsr_voxel_unique(*src.args(rule, voxel_size if voxel_size is not None else 1.0), coords.data_ptr(),
-                                         inverse.data_ptr(), first.data_ptr(), counts.data_ptr(),
-                                         None if points is None else points.data_ptr(), status.data_ptr(),
-                                         scratch.data_ptr(), flags, stream), "bsr_voxel_unique")
+        scratch = _ops.scratch(nbytes, dev)
+        _capi.call("bsr_voxel_unique", *src.args(rule, voxel_size if voxel_size is not None else 1.0),
+                   coords.data_ptr(), inverse.data_ptr(), first.data_ptr(), counts.data_ptr(), _ops.ptr(points),
+                   status.data_ptr(), scratch.data_ptr(), flags, _ops.stream(dev))
         st = [v & 0xffffffff for v in status.tolist()]          # the call's one host read
         raise_status(who, st)
         U = st[0]
@@ -229,14 +218,10 @@ def grow_level(anchor, offset, scaling, candidate_mask, anchor_feat, cur_size):
     from .densify import scatter_max, voxel_isin
     who = "grow_level"
     tensors = (("anchor", anchor), ("offset", offset), ("scaling", scaling), ("anchor_feat", anchor_feat))
-    for name, t in tensors + (("candidate_mask", candidate_mask),):
-        if not isinstance(t, torch.Tensor):
-            raise TypeError(f"{who}: {name} must be a torch.Tensor (got {type(t).__name__})")
-    for name, t in tensors:
-        if t.dtype != torch.float32:
-            raise TypeError(f"{who}: {name} must be float32 (got {t.dtype})")
-    if candidate_mask.dtype != torch.bool:
-        raise TypeError(f"{who}: candidate_mask must be bool (got {candidate_mask.dtype})")
+    mask = (("candidate_mask", candidate_mask),)
+    _ops.check_tensors(who, tensors + mask, None)     # (every operand a tensor before any dtype is looked at)
+    _ops.check_tensors(who, tensors, half_note=False)
+    _ops.check_tensors(who, mask, torch.bool)
     if anchor.dim() != 2 or anchor.shape[1] != 3:
         raise ValueError(f"{who}: anchor must be [N, 3] (got {list(anchor.shape)})")
     N = anchor.shape[0]
@@ -253,9 +238,7 @@ def grow_level(anchor, offset, scaling, candidate_mask, anchor_feat, cur_size):
     if N * K >= 2 ** 31:
         raise ValueError(f"{who}: need N * K below 2^31 (got {N} * {K})")
     cur_size = _check_size(who, cur_size)
-    for name, t in tensors + (("candidate_mask", candidate_mask),):
-        if t.device.type != "cuda":
-            raise ValueError(f"{who}: {name} must be on the GPU (there is no CPU path)")
+    _ops.check_on_gpu(who, tensors + mask)
     F = anchor_feat.shape[1]
     anchor, flat = anchor.detach().contiguous(), flat.detach().contiguous()
     scaling, scaling_stride = _strided_rows(scaling.detach())
