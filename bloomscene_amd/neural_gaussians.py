@@ -246,9 +246,11 @@ def render_anchors(anchor, grid_scaling, grid_offsets, neural_opacity, color, sc
     ``flags``: BSR_FLAG_* of the call; None = the calling thread's ``numerics(...)`` context.
     ``capacity`` (tile instances; extension): STATIC SHAPES and no host wait (include/bloomscene_anchors.h,
     BSR_FLAG_NO_READBACK) -- every per-Gaussian output then has N * K rows: the S selected Gaussians first, in the usual
-    order, then padding rows no camera sees (radii 0, zero gradients); S = mask.sum() stays on the device.  The image,
-    the depth and the gradients of the six inputs are bit-identical to the default mode's; a warmed-up forward +
-    backward can be captured into a HIP graph."""
+    order, then padding rows no camera sees (radii 0, zero gradients); S = mask.sum() stays on the device.  With at
+    least one candidate selected the image, the depth and the gradients of the six inputs are bit-identical to the
+    default mode's.  With nothing selected the static-shape mode renders the background and zero depth (all rows are
+    padding), where the default mode takes the P == 0 early return and gives zero images; gradients are zero in both.
+    A warmed-up forward + backward can be captured into a HIP graph."""
     from .numerics import resolve_flags
     return _NeuralRender.apply(anchor, grid_scaling, grid_offsets, neural_opacity, color, scale_rot, raster_settings,
                                bool(depth_gradient), resolve_flags() if flags is None else int(flags), capacity)

@@ -93,9 +93,13 @@ int bsr_anchor_expand_backward(int n_anchors, int n_offsets, int num_selected,
  * rows behind them are padded with Gaussians no camera can see (centre at cam_pos, opacity 0: culled by the rasterizer's
  * near-plane test, radii 0, zero gradient rows).  S itself stays on the device (word n_wg of anchor_scratch; the mask
  * holds the selection).  On entry *num_rendered = the rasterizer's capacity (tile instances); on return *num_selected
- * = N * K and *num_rendered = that capacity: hand both to bsr_anchor_render_backward.  The frame and every gradient of
- * the selected rows are bit-identical to the default path's.  Capturable into a hipGraph (after one warm-up call followed
- * by bsr_check_deferred(): see BSR_FLAG_NO_READBACK in bloomscene_rast.h). */
+ * = N * K and *num_rendered = that capacity: hand both to bsr_anchor_render_backward.  With at least one candidate
+ * selected, the frame and every gradient of the selected rows are bit-identical to the default path's.  With NOTHING
+ * selected the two modes differ: the default path hands the rasterizer P = 0 Gaussians and returns zero images (its
+ * early return, rasterize_points.cu:68-82), while this mode hands it N * K padding rows, so the frame is the
+ * BACKGROUND and the depth is zero; radii and all gradients are zero in both.  (S is not known on the host here, so
+ * there is no early return to take.)  Capturable into a hipGraph (after one warm-up call followed by
+ * bsr_check_deferred(): see BSR_FLAG_NO_READBACK in bloomscene_rast.h). */
 size_t bsr_anchor_gaussian_bytes(int num_selected);
 int bsr_anchor_render_forward(int n_anchors, int n_offsets,
                               const float* anchor, const float* grid_scaling, const float* grid_offsets,
