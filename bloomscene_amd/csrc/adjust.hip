@@ -2,8 +2,8 @@
 // prune + append of every per-anchor tensor.
 //
 //   k_decide_flags  a 256-thread workgroup owns one block of BSR_ADJUST_SCAN offsets (the first `blocks_o` workgroups) or
-//                   anchors (the rest): the flag bytes, and the block's counts of om / of kept rows and am from wave ballots
-//   k_decide_plan   a workgroup per block of anchors: the kept rows of the blocks before it (block_count.h), the rank of
+//                   anchors (the rest): the flag bytes, and the block's counts of om / of kept rows and am (wg_scan.h: wg_total)
+//   k_decide_plan   a workgroup per block of anchors: the kept rows of the blocks before it (wg_scan.h: wg_total_of), the rank of
 //                   each of its kept rows from wave ballots, src_of[rank] = row; workgroup 0 also adds up the status
 //   k_rows_resize   the multi-tensor shape of adam.hip: the descriptors travel in the kernel-argument block and a
 //                   workgroup finds its (tensor, chunk of BSR_RESIZE_CHUNK output elements) by a wave-uniform binary
@@ -14,15 +14,15 @@
 // [0, (n_keep + A) * width) of a dst.
 #include "common.h"
 #include "errors.h"
-#include "block_count.h"
+#include "wg_scan.h"
 #include "../../include/bloomscene_adjust.h"
 
 #include <cmath>
 
 namespace bsr {
 
-#define ADJ_BLOCK BSR_COUNT_BLOCK
-#define ADJ_WAVES BSR_COUNT_WAVES
+#define ADJ_BLOCK 256
+#define ADJ_WAVES (ADJ_BLOCK / 64)
 #define ADJ_SCAN BSR_ADJUST_SCAN
 #define ADJ_ROUNDS (ADJ_SCAN / ADJ_BLOCK)
 
@@ -63,9 +63,10 @@ __global__ void __launch_bounds__(ADJ_BLOCK) k_decide_flags(int N, int K, int bl
 				}
 				offset_flags[j] = (unsigned char)f;
 			}
-			n_om += (uint32_t)__popcll(wave_ballot(om));
+			n_om += om ? 1u : 0u;
 		}
-		block_store_count(n_om, part[0], om_count + blockIdx.x);
+		n_om = wg_total<ADJ_WAVES>(n_om, part[0]);
+		if (threadIdx.x == 0) om_count[blockIdx.x] = n_om;
 		return;
 	}
 	const int b = (int)blockIdx.x - blocks_o;
@@ -82,11 +83,15 @@ __global__ void __launch_bounds__(ADJ_BLOCK) k_decide_flags(int N, int K, int bl
 			keep = !prune;
 			anchor_flags[r] = (unsigned char)((prune ? BSR_ADJUST_ANCHOR_PRUNE : 0) | (am ? BSR_ADJUST_ANCHOR_VALID : 0));
 		}
-		n_keep += (uint32_t)__popcll(wave_ballot(keep));
-		n_am += (uint32_t)__popcll(wave_ballot(am));
+		n_keep += keep ? 1u : 0u;
+		n_am += am ? 1u : 0u;
 	}
-	block_store_count(n_keep, part[0], keep_count + b);
-	block_store_count(n_am, part[1], am_count + b);
+	n_keep = wg_total<ADJ_WAVES>(n_keep, part[0]);
+	n_am = wg_total<ADJ_WAVES>(n_am, part[1]);
+	if (threadIdx.x == 0) {
+		keep_count[b] = n_keep;
+		am_count[b] = n_am;
+	}
 }
 
 __global__ void __launch_bounds__(ADJ_BLOCK) k_decide_plan(int N, int blocks_a, int blocks_o,
@@ -100,9 +105,9 @@ __global__ void __launch_bounds__(ADJ_BLOCK) k_decide_plan(int N, int blocks_a, 
 	__shared__ uint32_t wave_count[ADJ_ROUNDS][ADJ_WAVES];
 	const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 	if (blockIdx.x == 0) {
-		const uint32_t kept = block_sum_counts(keep_count, blocks_a, part[1]);
-		const uint32_t am = block_sum_counts(am_count, blocks_a, part[2]);
-		const uint32_t om = block_sum_counts(om_count, blocks_o, part[3]);
+		const uint32_t kept = wg_total_of<ADJ_WAVES>(keep_count, blocks_a, part[1]);
+		const uint32_t am = wg_total_of<ADJ_WAVES>(am_count, blocks_a, part[2]);
+		const uint32_t om = wg_total_of<ADJ_WAVES>(om_count, blocks_o, part[3]);
 		if (threadIdx.x == 0) {
 			status[0] = kept;
 			status[1] = am;
@@ -110,7 +115,7 @@ __global__ void __launch_bounds__(ADJ_BLOCK) k_decide_plan(int N, int blocks_a, 
 			status[3] = 0;
 		}
 	}
-	uint32_t rank = block_sum_counts(keep_count, (int)blockIdx.x, part[0]);   // of the first kept row of this block
+	uint32_t rank = wg_total_of<ADJ_WAVES>(keep_count, (int)blockIdx.x, part[0]);   // of the first kept row of this block
 	bool keep[ADJ_ROUNDS];
 	uint32_t below[ADJ_ROUNDS];
 #pragma unroll

@@ -21,6 +21,7 @@
 // Nothing here dereferences an index it has not compared with the tensor's size first.
 #include "common.h"
 #include "mlp_rows.h"
+#include "wg_scan.h"
 #include "../../include/bloomscene_anchor_state.h"
 
 namespace bsr {
@@ -119,14 +120,8 @@ __global__ void __launch_bounds__(AST_BLOCK) k_visible_rate(int n, const unsigne
 	uint32_t count = 0;
 	for (int w = threadIdx.x; w < n / 4; w += AST_BLOCK) count += __popc(words[w] & 0x01010101u);
 	if ((int)threadIdx.x < n % 4) count += flags[n / 4 * 4 + threadIdx.x] & 1u;
-	count = wave_inclusive_sum_dpp(count);
-	if ((threadIdx.x & 63) == 63) wave_sum[threadIdx.x >> 6] = count;
-	__syncthreads();
-	if (threadIdx.x == 0) {
-		uint32_t total = 0;
-		for (int w = 0; w < AST_WAVES; w++) total += wave_sum[w];
-		rate[0] = (float)total / (float)n;   // (n == 0: 0 / 0)
-	}
+	const uint32_t total = wg_total<AST_WAVES>(count, wave_sum);
+	if (threadIdx.x == 0) rate[0] = (float)total / (float)n;   // (n == 0: 0 / 0)
 }
 
 enum { AST_G_COPY, AST_G_EXP, AST_G_MASK };
@@ -202,15 +197,10 @@ __global__ void __launch_bounds__(AST_BLOCK) k_accum_count(int N, int n, int K, 
 	for (int q = 0; q < AST_ROUNDS; q++) {
 		const long long c = (long long)blockIdx.x * AST_SCAN + q * AST_BLOCK + threadIdx.x;
 		const bool s = c < (long long)total && selection[c] != 0;
-		count += (uint32_t)__popcll(wave_ballot(s));   // (the same on every lane of the wave)
+		count += s ? 1u : 0u;
 	}
-	if ((threadIdx.x & 63) == 0) wave_sum[threadIdx.x >> 6] = count;
-	__syncthreads();
-	if (threadIdx.x == 0) {
-		uint32_t sum = 0;
-		for (int w = 0; w < AST_WAVES; w++) sum += wave_sum[w];
-		counts[blockIdx.x] = sum;
-	}
+	count = wg_total<AST_WAVES>(count, wave_sum);
+	if (threadIdx.x == 0) counts[blockIdx.x] = count;
 	for (long long i = (long long)blockIdx.x * AST_BLOCK + threadIdx.x; i < (long long)n; i += (long long)gridDim.x * AST_BLOCK) {
 		const long long r = idx[i];
 		if (r < 0 || r >= (long long)N) continue;
@@ -234,10 +224,7 @@ __global__ void __launch_bounds__(AST_BLOCK) k_accum_apply(int N, int n, int K, 
 	__shared__ uint32_t wave_count[AST_ROUNDS][AST_WAVES];
 	const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 	const int total = n * K;
-	uint32_t part = 0;
-	for (int b = threadIdx.x; b < (int)blockIdx.x; b += AST_BLOCK) part += counts[b];
-	part = wave_inclusive_sum_dpp(part);
-	if (lane == 63) before[wave] = part;
+	uint32_t rank = wg_total_of<AST_WAVES>(counts, (int)blockIdx.x, before);   // of the first candidate of this wave in round q
 	bool sel[AST_ROUNDS];
 	uint32_t below[AST_ROUNDS];
 #pragma unroll
@@ -249,8 +236,6 @@ __global__ void __launch_bounds__(AST_BLOCK) k_accum_apply(int N, int n, int K, 
 		if (lane == 0) wave_count[q][wave] = (uint32_t)__popcll(votes);
 	}
 	__syncthreads();
-	uint32_t rank = 0;   // of the first candidate of this wave in round q
-	for (int w = 0; w < AST_WAVES; w++) rank += before[w];
 #pragma unroll
 	for (int q = 0; q < AST_ROUNDS; q++) {
 		for (int w = 0; w < AST_WAVES; w++) {

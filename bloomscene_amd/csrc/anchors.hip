@@ -11,31 +11,13 @@
 // wave), and the K candidates of an anchor sit in one workgroup so the backward's per-anchor
 // sums are an LDS reduction in slot order -- no atomics, deterministic.
 #include "common.h"
+#include "wg_scan.h"
 #include "../../include/bloomscene_anchors.h"
 #include "../../include/bloomscene_rast.h"
 
 namespace bsr {
 
 #define BSR_ANCHOR_BLOCK 256
-
-// Exclusive prefix of `flag` over the workgroup's lanes (lane order), and the workgroup total.
-__device__ __forceinline__ uint32_t wg_prefix(bool flag, uint32_t* s_wave, uint32_t& total)
-{
-	const uint64_t b = __ballot(flag);
-	const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-	const uint32_t in_wave = (uint32_t)__popcll(b & ((1ull << lane) - 1ull));
-	if (lane == 0) s_wave[wave] = (uint32_t)__popcll(b);
-	__syncthreads();
-	uint32_t before = 0, all = 0;
-#pragma unroll
-	for (int w = 0; w < BSR_ANCHOR_BLOCK / 64; w++) {
-		const uint32_t c = s_wave[w];
-		before += (w < wave) ? c : 0u;
-		all += c;
-	}
-	total = all;
-	return before + in_wave;
-}
 
 __global__ void __launch_bounds__(BSR_ANCHOR_BLOCK) k_anchor_select(int n_cand, int per_wg,
                                                                     const float* __restrict__ neural_opacity,
@@ -49,7 +31,7 @@ __global__ void __launch_bounds__(BSR_ANCHOR_BLOCK) k_anchor_select(int n_cand, 
 	const bool sel = live && neural_opacity[i] > 0.0f;
 	if (live) mask[i] = sel ? 1 : 0;
 	uint32_t total;
-	wg_prefix(sel, s_wave, total);
+	wg_exclusive_count<BSR_ANCHOR_BLOCK / 64>(sel, s_wave, total);
 	if (t == 0) wg_count[blockIdx.x] = total;
 }
 
@@ -58,45 +40,9 @@ __global__ void __launch_bounds__(BSR_ANCHOR_BLOCK) k_anchor_select(int n_cand, 
 // barriers instead of 20 -- the kernel is pure latency.
 __global__ void __launch_bounds__(1024) k_anchor_scan(int n, uint32_t* __restrict__ wg_count)
 {
-	__shared__ uint32_t s_wave[16];
-	__shared__ uint32_t s_carry;
-	const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-	if (t == 0) s_carry = 0;
-	__syncthreads();
-	for (int base = 0; base < n; base += 8192) {
-		const int i0 = base + t * 8;
-		uint32_t v[8];
-#pragma unroll
-		for (int k = 0; k < 8; k++) v[k] = (i0 + k < n) ? wg_count[i0 + k] : 0u;
-		uint32_t mine = 0;
-#pragma unroll
-		for (int k = 0; k < 8; k++) mine += v[k];
-		uint32_t incl = mine;
-#pragma unroll
-		for (int d = 1; d < 64; d <<= 1) {
-			const uint32_t o = __shfl_up(incl, d);
-			if (lane >= d) incl += o;
-		}
-		if (lane == 63) s_wave[wave] = incl;
-		__syncthreads();
-		uint32_t before = s_carry, all = 0;
-#pragma unroll
-		for (int w = 0; w < 16; w++) {
-			const uint32_t c = s_wave[w];
-			before += (w < wave) ? c : 0u;
-			all += c;
-		}
-		uint32_t run = before + incl - mine;
-#pragma unroll
-		for (int k = 0; k < 8; k++) {
-			if (i0 + k < n) wg_count[i0 + k] = run;
-			run += v[k];
-		}
-		__syncthreads();
-		if (t == 0) s_carry += all;
-		__syncthreads();
-	}
-	if (t == 0) wg_count[n] = s_carry;
+	__shared__ uint32_t s_wave[2 * 16];
+	const uint32_t total = wg_exclusive_scan<16, 8>(n, wg_count, s_wave, true);
+	if (threadIdx.x == 0) wg_count[n] = total;
 }
 
 // ---- index list of the visible points (bsr_visible_filter_indices, SURVEY.md §8f rank 2, training half) ----
@@ -107,7 +53,7 @@ __global__ void __launch_bounds__(BSR_ANCHOR_BLOCK) k_visible_count(int P, const
 	__shared__ uint32_t s_wave[BSR_ANCHOR_BLOCK / 64];
 	const long long i = (long long)blockIdx.x * BSR_ANCHOR_BLOCK + threadIdx.x;
 	uint32_t total;
-	wg_prefix(i < P && radii[i] > 0, s_wave, total);
+	wg_exclusive_count<BSR_ANCHOR_BLOCK / 64>(i < P && radii[i] > 0, s_wave, total);
 	if (threadIdx.x == 0) wg_count[blockIdx.x] = total;
 }
 
@@ -118,8 +64,7 @@ __global__ void __launch_bounds__(BSR_ANCHOR_BLOCK) k_visible_compact(int P, con
 	__shared__ uint32_t s_wave[BSR_ANCHOR_BLOCK / 64];
 	const long long i = (long long)blockIdx.x * BSR_ANCHOR_BLOCK + threadIdx.x;
 	const bool vis = i < P && radii[i] > 0;
-	uint32_t total;
-	const uint32_t rank = wg_prefix(vis, s_wave, total);
+	const uint32_t rank = wg_exclusive_count<BSR_ANCHOR_BLOCK / 64>(vis, s_wave);
 	if (vis) visible_idx[wg_base[blockIdx.x] + rank] = (int)i;
 }
 
@@ -138,8 +83,7 @@ __global__ void __launch_bounds__(BSR_ANCHOR_BLOCK) k_anchor_expand(
 	const bool live = t < per_wg && i < n_cand;
 	const float nop = live ? neural_opacity[i] : 0.0f;
 	const bool sel = live && nop > 0.0f;
-	uint32_t total;
-	const uint32_t rank = wg_prefix(sel, s_wave, total);
+	const uint32_t rank = wg_exclusive_count<BSR_ANCHOR_BLOCK / 64>(sel, s_wave);
 	if (!sel) return;
 	const size_t dst = (size_t)wg_base[blockIdx.x] + rank;
 	const long long n = i / K;
@@ -177,8 +121,7 @@ __global__ void __launch_bounds__(BSR_ANCHOR_BLOCK) k_anchor_expand_bwd(
 	const long long i = (long long)blockIdx.x * per_wg + t;
 	const bool live = t < per_wg && i < n_cand;
 	const bool sel = live && neural_opacity[i] > 0.0f;
-	uint32_t total;
-	const uint32_t rank = wg_prefix(sel, s_wave, total);
+	const uint32_t rank = wg_exclusive_count<BSR_ANCHOR_BLOCK / 64>(sel, s_wave);
 	float part[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
 	if (live) {
 		float dn = 0.0f, dc[3] = {0, 0, 0}, dsr[7] = {0, 0, 0, 0, 0, 0, 0}, dof[3] = {0, 0, 0};

@@ -28,57 +28,9 @@
 // lane-scattered on MI355X: 0.2 ms at C3, 1.4 ms at C5); this one is also fully deterministic.
 #include "tile_sort.h"
 #include "launch.h"
+#include "wg_scan.h"
 
 namespace bsr {
-
-// Exclusive scan of n uint32 in place by ONE 1024-thread workgroup, 4 values per thread and step.
-// Returns the total to every thread.  s_wave: 32 words (two sets of 16 wave totals, used in turn).
-// One barrier per step: every thread adds up the sixteen wave totals itself (the carry lives in a register), and the
-// totals of consecutive steps go to alternating sets, so that a step's writes are two barriers behind the last reads
-// of the set they overwrite.  The next step's four values are requested before this step's barrier.  (Until round 6:
-// three barriers per step, the carry through LDS, a step beginning with the wait for its own loads -- a row of C5's
-// pass-1 histogram is five steps long: k_scans 34 -> .. us.)
-struct AllValid { __device__ __forceinline__ bool operator()(int) const { return true; } };
-template <typename Valid = AllValid>
-__device__ __forceinline__ uint32_t block_exclusive_scan(int n, uint32_t* data, uint32_t* s_wave, bool write, Valid valid = Valid())
-{
-	const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-	uint32_t carry = 0u;
-	uint32_t nx[4];
-#pragma unroll
-	for (int k = 0; k < 4; k++) nx[k] = (tid * 4 + k < n && valid(tid * 4 + k)) ? data[tid * 4 + k] : 0u;
-	int set = 0;
-	for (int base = 0; base < n; base += 4096, set ^= 16) {
-		const int i = base + tid * 4;
-		uint32_t v[4];
-#pragma unroll
-		for (int k = 0; k < 4; k++) v[k] = nx[k];
-#pragma unroll
-		for (int k = 0; k < 4; k++) nx[k] = (i + 4096 + k < n && valid(i + 4096 + k)) ? data[i + 4096 + k] : 0u;
-		const uint32_t mine = v[0] + v[1] + v[2] + v[3];
-		const uint32_t incl = wave_inclusive_sum_dpp(mine);
-		if (lane == 63) s_wave[set + wave] = incl;
-		__syncthreads();
-		uint32_t wave_off = 0u, total = 0u;
-#pragma unroll
-		for (int w = 0; w < 16; w++) {
-			const uint32_t t = s_wave[set + w];
-			wave_off += w < wave ? t : 0u;
-			total += t;
-		}
-		uint32_t run = carry + wave_off + incl - mine;
-		if (write) {
-#pragma unroll
-			for (int k = 0; k < 4; k++) {
-				if (i + k < n) data[i + k] = run;
-				run += v[k];
-			}
-		}
-		carry += total;
-	}
-	__syncthreads();   // (the caller may reuse s_wave at once)
-	return carry;
-}
 
 // The two scans between k_preprocess and the binning, in one launch:
 //  workgroup 256     : per-preprocess-workgroup totals: kept instances -> workgroup bases (in place) and
@@ -96,8 +48,8 @@ __global__ void __launch_bounds__(1024) k_scans(int n_wg, uint32_t* __restrict__
 {
 	__shared__ uint32_t s_w[32];
 	if (blockIdx.x == BSR_RADIX_BINS) {
-		const uint32_t kept = block_exclusive_scan(n_wg, wg_kept, s_w, true);
-		const uint32_t area = block_exclusive_scan(n_wg, wg_area, s_w, false);
+		const uint32_t kept = wg_exclusive_scan<16, 4>(n_wg, wg_kept, s_w, true);
+		const uint32_t area = wg_exclusive_scan<16, 4>(n_wg, wg_area, s_w, false);
 		if (threadIdx.x == 0) {
 			flags[2] = (int)kept;
 			flags[3] = (int)area;
@@ -118,8 +70,8 @@ __global__ void __launch_bounds__(1024) k_scans(int n_wg, uint32_t* __restrict__
 		return;
 	}
 	const int per = (n_wg + 7) >> 3, n_col = 8 * per;
-	const uint32_t total = block_exclusive_scan(n_col, hist1 + (size_t)blockIdx.x * n_col, s_w, true,
-	                                            Hist1ColumnValid{per, n_wg});
+	const uint32_t total = wg_exclusive_scan<16, 4>(n_col, hist1 + (size_t)blockIdx.x * n_col, s_w, true,
+	                                                Hist1ColumnValid{per, n_wg});
 	if (threadIdx.x == 0) hist1[(size_t)BSR_RADIX_BINS * n_col + blockIdx.x] = total;   // digit totals behind the rows
 }
 
@@ -148,34 +100,11 @@ __global__ void __launch_bounds__(256) k_radix_rowscan(const int* __restrict__ n
                                                        uint32_t* __restrict__ hist,
                                                        uint32_t* __restrict__ digit_total)
 {
-	__shared__ uint32_t s_wave[4];
-	__shared__ uint32_t s_carry;
+	__shared__ uint32_t s_wave[8];
 	const RadixPartition part = radix_partition(n_ptr, capacity, hist_blocks_max);
 	if (part.n <= 0) return;
-	const int n_blocks = part.n_blocks;
-	const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-	uint32_t* row = hist + (size_t)blockIdx.x * n_blocks;
-	if (tid == 0) s_carry = 0;
-	__syncthreads();
-	for (int base = 0; base < n_blocks; base += 256) {
-		const int i = base + tid;
-		const uint32_t v = (i < n_blocks) ? row[i] : 0u;
-		uint32_t incl = v;
-#pragma unroll
-		for (int d = 1; d < 64; d <<= 1) {
-			const uint32_t t = __shfl_up(incl, d, 64);
-			if (lane >= d) incl += t;
-		}
-		if (lane == 63) s_wave[wave] = incl;
-		__syncthreads();
-		const uint32_t w0 = s_wave[0], w1 = s_wave[1], w2 = s_wave[2], w3 = s_wave[3];
-		const uint32_t carry = s_carry;
-		if (i < n_blocks) row[i] = carry + (wave > 0 ? w0 : 0u) + (wave > 1 ? w1 : 0u) + (wave > 2 ? w2 : 0u) + incl - v;
-		__syncthreads();
-		if (tid == 0) s_carry = carry + w0 + w1 + w2 + w3;
-		__syncthreads();
-	}
-	if (tid == 0) digit_total[blockIdx.x] = s_carry;
+	const uint32_t total = wg_exclusive_scan<4, 1>(part.n_blocks, hist + (size_t)blockIdx.x * part.n_blocks, s_wave, true);
+	if (threadIdx.x == 0) digit_total[blockIdx.x] = total;
 }
 
 // ---- first radix pass, fused with the instance emit ----
@@ -216,7 +145,8 @@ __global__ void __launch_bounds__(256) k_emit_scatter(int P, int gx, const int* 
 	const uint64_t mask = kept_mask[ld];
 	const uint32_t depth_bits = __float_as_uint(depth[ld]);
 	{   // digit base = exclusive scan of the 256 digit totals (thread d <-> digit d) + this workgroup's prefix
-		const uint32_t incl = wave_inclusive_sum_dpp(v);   // (six __shfl_up steps are six ds_bpermute round trips)
+		// (wg_scan.h: wg_exclusive_sum, kept in its own text: the call compiles to another instruction stream here)
+		const uint32_t incl = wave_inclusive_sum_dpp(v);
 		if (lane == 63) s_scan[wave] = incl;
 		__syncthreads();
 		const uint32_t base = (wave > 0 ? s_scan[0] : 0u) + (wave > 1 ? s_scan[1] : 0u) + (wave > 2 ? s_scan[2] : 0u) + incl - v;
@@ -288,17 +218,7 @@ __global__ void __launch_bounds__(256) k_radix_scatter(const int* __restrict__ n
 	BinElem e_next = BinElem{0u, 0u, 0u};
 	if (beg + tid < end) e_next = load_elem(elems_in + beg + tid);
 	{   // digit base = exclusive scan of the 256 digit totals (thread d <-> digit d) + this block's row prefix
-		const uint32_t v = digit_total[tid];
-		uint32_t incl = v;
-#pragma unroll
-		for (int d = 1; d < 64; d <<= 1) {
-			const uint32_t t = __shfl_up(incl, d, 64);
-			if (lane >= d) incl += t;
-		}
-		if (lane == 63) s_scan[wave] = incl;
-		__syncthreads();
-		const uint32_t base = (wave > 0 ? s_scan[0] : 0u) + (wave > 1 ? s_scan[1] : 0u) + (wave > 2 ? s_scan[2] : 0u) + incl - v;
-		s_off[tid] = base + row_prefix;
+		s_off[tid] = wg_exclusive_sum<4>(digit_total[tid], s_scan) + row_prefix;
 	}
 #pragma unroll
 	for (int w = 0; w < 4; w++) s_wcnt[w][tid] = 0;
@@ -357,11 +277,8 @@ struct BucketSlice { int beg, end; };
 __device__ __forceinline__ BucketSlice bucket_slice(uint32_t my_total, int d1, int s, int n_slices, uint32_t* s_scan,
                                                     uint32_t* s_base)
 {
-	const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-	const uint32_t incl = wave_inclusive_sum_dpp(my_total);
-	if (lane == 63) s_scan[wave] = incl;
-	__syncthreads();
-	const uint32_t base = (wave > 0 ? s_scan[0] : 0u) + (wave > 1 ? s_scan[1] : 0u) + (wave > 2 ? s_scan[2] : 0u) + incl - my_total;
+	const int tid = threadIdx.x;
+	const uint32_t base = wg_exclusive_sum<4>(my_total, s_scan);
 	if (tid == d1) {
 		s_base[0] = base;
 		s_base[1] = my_total;

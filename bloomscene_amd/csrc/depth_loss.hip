@@ -14,10 +14,11 @@
 // and forms all 25 taps from LDS.  A 32-lane half reads 32 consecutive words of one row; the row stride is odd (37) so
 // that the staging loop, whose halves straddle rows of 36, is conflict-free too.  rgb is read in place through its
 // three strides.
-// SUMS.  The header: per thread in fp64 in tile order, per workgroup a butterfly and four wave results added in order,
-// one partial per sum per workgroup in the scratch; the workgroup that draws the last ticket adds them the same way.
-// No float atomics; the only atomics are the integer tickets.
+// SUMS.  The header: per thread in fp64 in tile order, then grid_sum.h (which states the order) with one partial per
+// sum per workgroup in the scratch; the extrema kernels use its ticket alone.  No float atomics; the only atomics are
+// the integer tickets.
 #include "common.h"
+#include "grid_sum.h"
 #include "../../include/bloomscene_depth_loss.h"
 
 namespace bsr {
@@ -99,64 +100,6 @@ __device__ __forceinline__ int clampi(int v, int hi) { return v < 0 ? 0 : (v > h
 // r or o of one depth
 __device__ __forceinline__ float depth_norm(float v, float lo, float rg, int normalise) { return normalise ? (v - lo) / rg : v; }
 
-__device__ __forceinline__ double load_f64(const double* p)
-{
-	return __longlong_as_double((long long)__hip_atomic_load((const unsigned long long*)p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-}
-__device__ __forceinline__ unsigned load_u32(const unsigned* p)
-{
-	return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// thread 0 draws the workgroup's ticket (after its partial is stored) -> whether this workgroup is the last, to all
-__device__ __forceinline__ bool depth_last_ticket(unsigned* ticket)
-{
-	__shared__ int s_last;
-	__syncthreads();
-	if (threadIdx.x == 0) {
-		__threadfence();
-		s_last = atomicAdd(ticket, 1u) == gridDim.x - 1;
-	}
-	__syncthreads();
-	const bool last = s_last != 0;
-	if (last) __threadfence();
-	return last;
-}
-
-// The workgroup's sums v[0..N) -> its N partials; the last workgroup to arrive adds the partials.  Returns true in
-// thread 0 of that workgroup, with the totals in v.  Every thread of every workgroup must call it.
-template <int N>
-__device__ __forceinline__ bool depth_grid_sum(double (&v)[N], unsigned* ticket, double* psum)
-{
-	__shared__ double s_w[N][BSR_DEPTH_BLOCK / 64];
-	const int tid = threadIdx.x, wave = tid >> 6;
-	for (int pass = 0; pass < 2; pass++) {
-#pragma unroll
-		for (int k = 0; k < N; k++)
-			for (int o = 32; o > 0; o >>= 1) v[k] += __shfl_xor(v[k], o);
-		if ((tid & 63) == 0) {
-#pragma unroll
-			for (int k = 0; k < N; k++) s_w[k][wave] = v[k];
-		}
-		__syncthreads();
-#pragma unroll
-		for (int k = 0; k < N; k++) v[k] = ((s_w[k][0] + s_w[k][1]) + s_w[k][2]) + s_w[k][3];
-		__syncthreads();
-		if (pass == 1) return tid == 0;
-		if (tid == 0) {
-#pragma unroll
-			for (int k = 0; k < N; k++) psum[N * (size_t)blockIdx.x + k] = v[k];
-		}
-		if (!depth_last_ticket(ticket)) return false;
-#pragma unroll
-		for (int k = 0; k < N; k++) v[k] = 0.0;
-		for (unsigned b = tid; b < gridDim.x; b += BSR_DEPTH_BLOCK)
-#pragma unroll
-			for (int k = 0; k < N; k++) v[k] += load_f64(&psum[N * (size_t)b + k]);
-	}
-	return false;
-}
-
 // (lo, n_lo) and (hi, n_hi) of two sets: exact whatever the order
 __device__ __forceinline__ void extrema_add(Extrema& a, float lo, unsigned n_lo, float hi, unsigned n_hi)
 {
@@ -211,7 +154,7 @@ __global__ void __launch_bounds__(BSR_DEPTH_BLOCK) k_depth_extrema(long long n, 
 		part[blockIdx.x].d = d;
 		part[blockIdx.x].p = p;
 	}
-	if (!depth_last_ticket(&sc.ticket[TICKET_EXTREMA])) return;
+	if (!grid_last_ticket(&sc.ticket[TICKET_EXTREMA])) return;
 	d = extrema_none();
 	p = extrema_none();
 	for (unsigned b = tid; b < gridDim.x; b += BSR_DEPTH_BLOCK) {
@@ -253,7 +196,7 @@ __global__ void __launch_bounds__(BSR_DEPTH_BLOCK) k_depth_maxdiff(long long n, 
 	}
 	extrema_block(m);
 	if (tid == 0) part[blockIdx.x] = m;
-	if (!depth_last_ticket(&sc.ticket[TICKET_MAXDIFF])) return;
+	if (!grid_last_ticket(&sc.ticket[TICKET_MAXDIFF])) return;
 	m = extrema_none();
 	for (unsigned b = tid; b < gridDim.x; b += BSR_DEPTH_BLOCK) {
 		const unsigned* w = (const unsigned*)&part[b];
@@ -385,7 +328,7 @@ __global__ void __launch_bounds__(BSR_DEPTH_BLOCK) k_depth_sums(DepthShape s, co
 		}
 		__syncthreads();   // (the next tile's staging overwrites what this pass read)
 	}
-	if (depth_grid_sum<BSR_DEPTH_NSUM>(sums, &sc.ticket[TICKET_SUMS], sc.psum)) {
+	if (grid_sum<BSR_DEPTH_NSUM, BSR_DEPTH_BLOCK>(sums, &sc.ticket[TICKET_SUMS], sc.psum)) {
 		double Lv = 0.0, Ld = 0.0, Ls = 0.0, loss = 0.0;
 		if (value) {
 			Lv = sums[SUM_X] / (double)((long long)s.H * (s.W - 1)) + sums[SUM_Y] / (double)((long long)(s.H - 1) * s.W);
@@ -507,7 +450,7 @@ __global__ void __launch_bounds__(BSR_DEPTH_BLOCK) k_depth_grad(DepthShape s, co
 		__syncthreads();
 	}
 	if (!s.normalise) return;   // (uniform over the grid)
-	if (depth_grid_sum<2>(sums, &sc.ticket[TICKET_GRAD], sc.psum)) {
+	if (grid_sum<2, BSR_DEPTH_BLOCK>(sums, &sc.ticket[TICKET_GRAD], sc.psum)) {
 		sc.gsum[0] = sums[0];
 		sc.gsum[1] = sums[1];
 	}

@@ -10,14 +10,14 @@
 // t, t + G, ... and the r columns of each entry in order, so the sum over the columns of one weight entry stays inside one
 // lane; the sum over a row (the gradient of a per-row q) is per lane in column order, then a butterfly over the
 // group.  A row that is not chosen is left (or zero-filled) before any operand is loaded.
-// SUMS.  total, count and the gradient of a single q: per thread in fp64 in index order, per workgroup a butterfly and
-// four wave results added in order, one partial per workgroup in the scratch; the workgroup that draws the last ticket
-// adds the partials the same way and rounds once.  The grid depends on (n, C, r) alone: bit-identical from run to run.
+// SUMS.  total, count and the gradient of a single q: per thread in fp64 in index order, then grid_sum.h (which states
+// the order), rounded once at the end.  The grid depends on (n, C, r) alone: bit-identical from run to run.
 // No float atomics; the only atomic is the integer ticket.
 // ARITHMETIC.  Per element two erf / erfc (one exp and a polynomial for a narrow bin), one log2 (forward), two exp, one
 // expm1 and one division by l (backward), all from the device library: at BloomScene's shape (100 k rows, 5 % chosen, 86 columns over the three calls) that is
 // 4.3e5 elements a step, and the kernels are bound by the rows they skip or zero-fill, not by these.
 #include "common.h"
+#include "grid_sum.h"
 #include "../../include/bloomscene_entropy.h"
 
 namespace bsr {
@@ -36,11 +36,11 @@ struct EntropyOperands {
 	const float* w;
 };
 
-// scratch: [0, 4) the ticket; from BSR_ENTROPY_HEAD one fp64 per workgroup, then one uint32 per workgroup
+// scratch: [0, 4) the ticket; from BSR_ENTROPY_HEAD two fp64 per workgroup (the sum, then the chosen rows -- a count
+// carried in fp64 is exact: it and every partial sum of it are integers below 2^31)
 struct EntropyScratch {
 	unsigned* ticket;
 	double* psum;
-	unsigned* pcnt;
 };
 
 static unsigned entropy_lg(int Cw)
@@ -58,12 +58,11 @@ static unsigned entropy_blocks(long long tiles)
 {
 	return (unsigned)(tiles < 1 ? 1 : (tiles < BSR_ENTROPY_MAX_BLOCKS ? tiles : BSR_ENTROPY_MAX_BLOCKS));
 }
-static EntropyScratch entropy_scratch(void* scratch, unsigned blocks)
+static EntropyScratch entropy_scratch(void* scratch)
 {
 	EntropyScratch s;
 	s.ticket = (unsigned*)scratch;
 	s.psum = (double*)((char*)scratch + BSR_ENTROPY_HEAD);
-	s.pcnt = (unsigned*)(s.psum + blocks);
 	return s;
 }
 
@@ -134,45 +133,6 @@ __device__ __forceinline__ double group_sum(double v, int G)   // over the G lan
 	return v;
 }
 
-// The workgroup's sum of (v, c) -> its partial; the last workgroup to arrive adds the partials.  Returns true in thread 0
-// of that workgroup, with the totals in v and c.  Every thread of every workgroup must call it.
-__device__ __forceinline__ bool grid_sum(double& v, unsigned long long& c, const EntropyScratch& sc)
-{
-	__shared__ double s_v[BSR_ENTROPY_BLOCK / 64];
-	__shared__ unsigned long long s_c[BSR_ENTROPY_BLOCK / 64];
-	__shared__ int s_last;
-	const int tid = threadIdx.x, wave = tid >> 6;
-	for (int pass = 0; pass < 2; pass++) {
-		for (int o = 32; o > 0; o >>= 1) {
-			v += __shfl_xor(v, o);
-			c += __shfl_xor(c, o);
-		}
-		if ((tid & 63) == 0) { s_v[wave] = v; s_c[wave] = c; }
-		__syncthreads();
-		v = ((s_v[0] + s_v[1]) + s_v[2]) + s_v[3];
-		c = s_c[0] + s_c[1] + s_c[2] + s_c[3];
-		__syncthreads();
-		if (pass == 1) return tid == 0;
-		if (tid == 0) {
-			sc.psum[blockIdx.x] = v;
-			sc.pcnt[blockIdx.x] = (unsigned)c;   // (< 2^31 rows in all)
-			__threadfence();
-			s_last = atomicAdd(sc.ticket, 1u) == gridDim.x - 1;
-		}
-		__syncthreads();
-		if (!s_last) return false;
-		__threadfence();
-		v = 0.0;
-		c = 0ull;
-		for (unsigned b = tid; b < gridDim.x; b += BSR_ENTROPY_BLOCK) {
-			v += __longlong_as_double((long long)__hip_atomic_load((unsigned long long*)&sc.psum[b], __ATOMIC_RELAXED,
-			                                                       __HIP_MEMORY_SCOPE_AGENT));
-			c += __hip_atomic_load(&sc.pcnt[b], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-		}
-	}
-	return false;
-}
-
 __global__ void __launch_bounds__(BSR_ENTROPY_BLOCK) k_entropy_fwd(EntropyOperands a, float* __restrict__ bits,
                                                                    float* __restrict__ likelihood,
                                                                    float* __restrict__ total, long long* __restrict__ count,
@@ -180,8 +140,7 @@ __global__ void __launch_bounds__(BSR_ENTROPY_BLOCK) k_entropy_fwd(EntropyOperan
 {
 	const int G = 1 << a.lg, lane = threadIdx.x & (G - 1), rib = threadIdx.x >> a.lg, R = BSR_ENTROPY_BLOCK >> a.lg;
 	const float xm = a.x_mean[0];
-	double acc = 0.0;
-	unsigned long long chosen = 0ull;
+	double sums[2] = {0.0, 0.0};   // the bits, the chosen rows
 	for (long long tile = blockIdx.x; tile < a.tiles; tile += gridDim.x) {
 		const long long i = tile * R + rib;
 		if (i >= (long long)a.n) continue;
@@ -192,7 +151,7 @@ __global__ void __launch_bounds__(BSR_ENTROPY_BLOCK) k_entropy_fwd(EntropyOperan
 			}
 			continue;
 		}
-		if (lane == 0) chosen++;
+		if (lane == 0) sums[1] += 1.0;
 		const float qrow = a.q_mode == BSR_ENTROPY_Q_SINGLE ? a.q[0] : (a.q_mode == BSR_ENTROPY_Q_ROW ? a.q[i] : 0.0f);
 		for (int jw = lane; jw < a.Cw; jw += G) {
 			const float wv = a.w ? a.w[i * a.Cw + jw] : 1.0f;
@@ -205,14 +164,14 @@ __global__ void __launch_bounds__(BSR_ENTROPY_BLOCK) k_entropy_fwd(EntropyOperan
 				const float term = a.w ? b * wv : b;
 				if (bits) bits[i * a.C + j] = term;
 				if (likelihood) likelihood[i * a.C + j] = l;
-				acc += (double)term;
+				sums[0] += (double)term;
 			}
 		}
 	}
 	if (!total && !count) return;   // (uniform: no sums asked for)
-	if (grid_sum(acc, chosen, sc)) {
-		if (total) total[0] = (float)acc;
-		if (count) count[0] = (long long)chosen * (long long)a.C;
+	if (grid_sum<2, BSR_ENTROPY_BLOCK>(sums, sc.ticket, sc.psum)) {
+		if (total) total[0] = (float)sums[0];
+		if (count) count[0] = (long long)sums[1] * (long long)a.C;
 	}
 }
 
@@ -225,7 +184,7 @@ __global__ void __launch_bounds__(BSR_ENTROPY_BLOCK) k_entropy_bwd(EntropyOperan
 	const float xm = a.x_mean[0];
 	const float g_single = g_mode == BSR_ENTROPY_G_SINGLE ? g[0] : 0.0f;
 	const bool dq_row = dq && a.q_mode != BSR_ENTROPY_Q_ELEMENT;
-	double acc = 0.0;   // the gradient of a single q
+	double acc[1] = {0.0};   // the gradient of a single q
 	for (long long tile = blockIdx.x; tile < a.tiles; tile += gridDim.x) {
 		const long long i = tile * R + rib;
 		if (i >= (long long)a.n) continue;
@@ -284,13 +243,12 @@ __global__ void __launch_bounds__(BSR_ENTROPY_BLOCK) k_entropy_bwd(EntropyOperan
 			const double row = group_sum(dq_lane, G);
 			if (lane == 0) {
 				if (a.q_mode == BSR_ENTROPY_Q_ROW) dq[i] = (float)row;
-				else acc += row;
+				else acc[0] += row;
 			}
 		}
 	}
 	if (!(dq && a.q_mode == BSR_ENTROPY_Q_SINGLE)) return;   // (uniform)
-	unsigned long long unused = 0ull;
-	if (grid_sum(acc, unused, sc)) dq[0] = (float)acc;
+	if (grid_sum<1, BSR_ENTROPY_BLOCK>(acc, sc.ticket, sc.psum)) dq[0] = (float)acc[0];
 }
 
 // the checks both entry points share; fills the operands
@@ -327,7 +285,7 @@ size_t bsr_entropy_scratch_bytes(int n, int C, int r)
 {
 	if (n < 0 || C < 1 || r < 1 || C % r != 0) return 0;
 	const unsigned blocks = entropy_blocks(entropy_tiles(n, entropy_lg(C / r)));
-	return align_up(BSR_ENTROPY_HEAD + (size_t)blocks * (sizeof(double) + sizeof(unsigned)), 256);
+	return align_up(BSR_ENTROPY_HEAD + (size_t)blocks * 2 * sizeof(double), 256);
 }
 
 int bsr_entropy_forward(int n, int C, int r, const float* x, long long xs, const float* mean, long long ms,
@@ -351,7 +309,7 @@ int bsr_entropy_forward(int n, int C, int r, const float* x, long long xs, const
 	const unsigned blocks = entropy_blocks(a.tiles);
 	EntropyScratch sc = {};
 	if (sums) {
-		sc = entropy_scratch(scratch, blocks);
+		sc = entropy_scratch(scratch);
 		if (hipMemsetAsync(sc.ticket, 0, sizeof(unsigned), st) != hipSuccess) return fail("%s: memset failed", who);
 	}
 	hipLaunchKernelGGL(k_entropy_fwd, dim3(blocks), dim3(BSR_ENTROPY_BLOCK), 0, st, a, bits, likelihood, total, count, sc);
@@ -383,7 +341,7 @@ int bsr_entropy_backward(int n, int C, int r, const float* x, long long xs, cons
 	const unsigned blocks = entropy_blocks(a.tiles);
 	EntropyScratch sc = {};
 	if (sums) {
-		sc = entropy_scratch(scratch, blocks);
+		sc = entropy_scratch(scratch);
 		if (hipMemsetAsync(sc.ticket, 0, sizeof(unsigned), st) != hipSuccess) return fail("%s: memset failed", who);
 	}
 	hipLaunchKernelGGL(k_entropy_bwd, dim3(blocks), dim3(BSR_ENTROPY_BLOCK), 0, st, a, g, g_mode, dx, dmean, dscale, dq, dw, sc);

@@ -28,6 +28,7 @@
 // are never candidates; padding slots hold NaN, whose d is NaN and never counts.  So the result does not depend on the
 // order, the box sizes or the bounds: it is the header's function of the input.
 #include "common.h"
+#include "wg_scan.h"
 #include "../../include/bloomscene_knn.h"
 
 namespace bsr {
@@ -199,28 +200,9 @@ __global__ void __launch_bounds__(BSR_KNN_BLOCK) k_knn_hist(int P, const uint32_
 __global__ void __launch_bounds__(BSR_KNN_BLOCK) k_knn_rowscan(int n_tiles, uint32_t* __restrict__ hist,
                                                                uint32_t* __restrict__ totals)
 {
-	__shared__ uint32_t s_w[4];
-	const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-	uint32_t* row = hist + (size_t)blockIdx.x * n_tiles;
-	uint32_t carry = 0u;
-	for (int b = 0; b < n_tiles; b += BSR_KNN_BLOCK) {
-		const int i = b + tid;
-		const uint32_t v = i < n_tiles ? row[i] : 0u;
-		const uint32_t incl = wave_inclusive_sum_dpp(v);
-		if (lane == 63) s_w[wave] = incl;
-		__syncthreads();
-		uint32_t off = 0u, tot = 0u;
-#pragma unroll
-		for (int w = 0; w < 4; w++) {
-			const uint32_t t = s_w[w];
-			off += w < wave ? t : 0u;
-			tot += t;
-		}
-		if (i < n_tiles) row[i] = carry + off + incl - v;
-		carry += tot;
-		__syncthreads();
-	}
-	if (tid == 0) totals[blockIdx.x] = carry;
+	__shared__ uint32_t s_w[2 * (BSR_KNN_BLOCK / 64)];
+	const uint32_t total = wg_exclusive_scan<BSR_KNN_BLOCK / 64, 1>(n_tiles, hist + (size_t)blockIdx.x * n_tiles, s_w, true);
+	if (threadIdx.x == 0) totals[blockIdx.x] = total;
 }
 
 // Tile t: wave w owns keys [t * 4096 + w * 1024, + 1024), 16 chunks of 64 in order.  A key's place = the digit's base
@@ -235,15 +217,9 @@ __global__ void __launch_bounds__(BSR_KNN_BLOCK) k_knn_scatter(int P, const uint
 	__shared__ uint32_t s_run[4][256];
 	__shared__ uint32_t s_w[4];
 	const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-	const uint32_t tot = totals[tid];
-	const uint32_t incl = wave_inclusive_sum_dpp(tot);
-	if (lane == 63) s_w[wave] = incl;
 #pragma unroll
 	for (int w = 0; w < 4; w++) s_run[w][tid] = 0u;
-	__syncthreads();
-	uint32_t run = incl - tot + hist[(size_t)tid * n_tiles + blockIdx.x];
-#pragma unroll
-	for (int w = 0; w < 4; w++) run += w < wave ? s_w[w] : 0u;
+	uint32_t run = wg_exclusive_sum<4>(totals[tid], s_w) + hist[(size_t)tid * n_tiles + blockIdx.x];   // (its barrier covers the zeroes too)
 	const size_t wbase = (size_t)blockIdx.x * BSR_KNN_TILE + (size_t)wave * (BSR_KNN_TILE / 4);
 	constexpr int CHUNKS = BSR_KNN_TILE / 4 / 64;
 	for (int c = 0; c < CHUNKS; c++) {

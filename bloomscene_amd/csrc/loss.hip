@@ -12,12 +12,12 @@
 // LDS BANKS.  ds_read_b32 conflicts count per 32-lane half.  A half always holds 32 consecutive x of ONE row (both passes
 // are indexed row * 32 + x), so every access is to 32 consecutive words whatever the row stride; the strides are odd (43
 // and 33) all the same, so that the staging loop, whose halves straddle rows of 42, stays conflict-free too.
-// SUMS.  bloomscene_loss.h: per thread in fp64 in tile order, per workgroup a butterfly and four wave results added in order,
-// two partials per workgroup in the scratch; the workgroup that draws the last ticket adds them the same way.  No float
-// atomics; the only atomic is the integer ticket.
+// SUMS.  bloomscene_loss.h: per thread in fp64 in tile order, then grid_sum.h (which states the order) with two partials
+// per workgroup in the scratch.  No float atomics; the only atomic is the integer ticket.
 // COST.  About 380 fp32 operations and 93 LDS reads a pixel forward, 185 and 87 backward.  At [3, 512, 512] that is 1536
 // tiles, one round of resident workgroups (26 KB of LDS: six a CU), and 0.09 ms for both kernels (docs/EXPERIMENTS.md).
 #include "common.h"
+#include "grid_sum.h"
 #include "../../include/bloomscene_loss.h"
 
 namespace bsr {
@@ -97,46 +97,6 @@ __device__ __forceinline__ float column_pass(const float* rows, int x, int y)
 	return acc;
 }
 
-// The workgroup's sums of (u, v) -> its two partials; the last workgroup to arrive adds the partials.  Returns true in
-// thread 0 of that workgroup, with the totals in u and v.  Every thread of every workgroup must call it.
-__device__ __forceinline__ bool loss_grid_sum(double& u, double& v, const LossScratch& sc)
-{
-	__shared__ double s_u[BSR_LOSS_BLOCK / 64];
-	__shared__ double s_v[BSR_LOSS_BLOCK / 64];
-	__shared__ int s_last;
-	const int tid = threadIdx.x, wave = tid >> 6;
-	for (int pass = 0; pass < 2; pass++) {
-		for (int o = 32; o > 0; o >>= 1) {
-			u += __shfl_xor(u, o);
-			v += __shfl_xor(v, o);
-		}
-		if ((tid & 63) == 0) { s_u[wave] = u; s_v[wave] = v; }
-		__syncthreads();
-		u = ((s_u[0] + s_u[1]) + s_u[2]) + s_u[3];
-		v = ((s_v[0] + s_v[1]) + s_v[2]) + s_v[3];
-		__syncthreads();
-		if (pass == 1) return tid == 0;
-		if (tid == 0) {
-			sc.psum[2 * (size_t)blockIdx.x] = u;
-			sc.psum[2 * (size_t)blockIdx.x + 1] = v;
-			__threadfence();
-			s_last = atomicAdd(sc.ticket, 1u) == gridDim.x - 1;
-		}
-		__syncthreads();
-		if (!s_last) return false;
-		__threadfence();
-		u = 0.0;
-		v = 0.0;
-		for (unsigned b = tid; b < gridDim.x; b += BSR_LOSS_BLOCK) {
-			u += __longlong_as_double((long long)__hip_atomic_load((unsigned long long*)&sc.psum[2 * (size_t)b], __ATOMIC_RELAXED,
-			                                                       __HIP_MEMORY_SCOPE_AGENT));
-			v += __longlong_as_double((long long)__hip_atomic_load((unsigned long long*)&sc.psum[2 * (size_t)b + 1], __ATOMIC_RELAXED,
-			                                                       __HIP_MEMORY_SCOPE_AGENT));
-		}
-	}
-	return false;
-}
-
 __global__ void __launch_bounds__(BSR_LOSS_BLOCK) k_photometric_fwd(LossShape s, const float* __restrict__ img,
                                                                     const float* __restrict__ gt, float lambda,
                                                                     float* __restrict__ partials, float* __restrict__ ssim_map,
@@ -146,7 +106,7 @@ __global__ void __launch_bounds__(BSR_LOSS_BLOCK) k_photometric_fwd(LossShape s,
 	__shared__ float s_row[5][BSR_LOSS_ROW_WORDS];   // the row pass of img, gt, img img, gt gt, img gt
 	const int tid = threadIdx.x;
 	const long long N = s.planes * (long long)s.H * (long long)s.W;
-	double sum_l1 = 0.0, sum_m = 0.0;
+	double sums[2] = {0.0, 0.0};   // |img - gt|, m
 	for (long long tile = blockIdx.x; tile < s.tiles; tile += gridDim.x) {
 		const LossTile t = loss_tile(s, tile);
 		stage_tile(s, t, img, s_in[0]);
@@ -198,14 +158,14 @@ __global__ void __launch_bounds__(BSR_LOSS_BLOCK) k_photometric_fwd(LossShape s,
 			}
 			if (ssim_map) ssim_map[at] = m;
 			const int centre = (y + BSR_LOSS_HALO) * BSR_LOSS_IN_STRIDE + x + BSR_LOSS_HALO;
-			sum_l1 += (double)fabsf(s_in[0][centre] - s_in[1][centre]);
-			sum_m += (double)m;
+			sums[0] += (double)fabsf(s_in[0][centre] - s_in[1][centre]);
+			sums[1] += (double)m;
 		}
 		__syncthreads();   // (the next tile's staging overwrites what this pass read)
 	}
-	if (loss_grid_sum(sum_l1, sum_m, sc)) {
+	if (grid_sum<2, BSR_LOSS_BLOCK>(sums, sc.ticket, sc.psum)) {
 		const double n = (double)N, lam = (double)lambda;
-		const double l1 = sum_l1 / n, ssim = sum_m / n;
+		const double l1 = sums[0] / n, ssim = sums[1] / n;
 		const double first = (1.0 - lam) * l1, second = lam * (1.0 - ssim);
 		out[0] = (float)(first + second);
 		out[1] = (float)l1;

@@ -9,7 +9,7 @@
 //   k_voxel_pack      key[e] = (x - xmin) << (by + bz) | (y - ymin) << bz | (z - zmin), payload[e] = e; workgroup 0
 //                     writes the widths to the header and the status
 //   k_voxel_hist / k_voxel_rowscan / k_voxel_scatter   one stable LSD radix pass on an 8-bit digit of the key, in the form
-//                     of binning.hip's k_radix_* (digit-major histogram, 256 row scans, wave ballots for the in-round
+//                     of binning.hip's k_radix_* (digit-major histogram, 256 row scans (wg_scan.h), wave ballots for the in-round
 //                     rank, stamped per-wave counters across the four waves).  Eight passes are enqueued; a pass whose
 //                     digit lies above the key width returns at once, and the buffer that holds the result follows from
 //                     the same header word -- the host never reads the width.
@@ -22,11 +22,13 @@
 // WHY IT IS DETERMINISTIC.  Integer minimum, maximum and sum do not depend on the order of their operands; every other
 // word is written by exactly one thread whose identity follows from the input alone.
 #include "errors.h"
+#include "wg_scan.h"
 #include "../../include/bloomscene_voxelize.h"
 
 namespace bsr {
 
 #define BSR_VX_BLOCK 256
+#define BSR_VX_WAVES (BSR_VX_BLOCK / 64)
 #define BSR_VX_BINS 256
 #define BSR_VX_QUANT_BLOCKS 2048     // the quantise kernel strides beyond this many workgroups
 #define BSR_VX_SORT_BLOCKS 2048      // most workgroups (histogram columns) of a sort pass
@@ -233,27 +235,10 @@ __global__ void __launch_bounds__(BSR_VX_BLOCK) k_voxel_rowscan(int n_blocks, in
                                                                 uint32_t* __restrict__ hist,
                                                                 uint32_t* __restrict__ digit_total)
 {
-	__shared__ uint32_t s_wave[4];
-	__shared__ uint32_t s_carry;
+	__shared__ uint32_t s_wave[2 * BSR_VX_WAVES];
 	if (!vx_pass_active(hdr, shift)) return;
-	const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-	uint32_t* row = hist + (size_t)blockIdx.x * n_blocks;
-	if (tid == 0) s_carry = 0u;
-	__syncthreads();
-	for (int base = 0; base < n_blocks; base += BSR_VX_BLOCK) {
-		const int i = base + tid;
-		const uint32_t v = (i < n_blocks) ? row[i] : 0u;
-		const uint32_t incl = wave_inclusive_sum_dpp(v);
-		if (lane == 63) s_wave[wave] = incl;
-		__syncthreads();
-		const uint32_t w0 = s_wave[0], w1 = s_wave[1], w2 = s_wave[2], w3 = s_wave[3];
-		const uint32_t carry = s_carry;
-		if (i < n_blocks) row[i] = carry + (wave > 0 ? w0 : 0u) + (wave > 1 ? w1 : 0u) + (wave > 2 ? w2 : 0u) + incl - v;
-		__syncthreads();
-		if (tid == 0) s_carry = carry + w0 + w1 + w2 + w3;
-		__syncthreads();
-	}
-	if (tid == 0) digit_total[blockIdx.x] = s_carry;
+	const uint32_t total = wg_exclusive_scan<BSR_VX_WAVES, 1>(n_blocks, hist + (size_t)blockIdx.x * n_blocks, s_wave, true);
+	if (threadIdx.x == 0) digit_total[blockIdx.x] = total;
 }
 
 __global__ void __launch_bounds__(BSR_VX_BLOCK) k_voxel_scatter(int E, int chunk, int n_blocks, int shift,
@@ -273,12 +258,7 @@ __global__ void __launch_bounds__(BSR_VX_BLOCK) k_voxel_scatter(int E, int chunk
 	const size_t beg = (size_t)blockIdx.x * chunk, end = min((size_t)E, beg + chunk);
 	const uint32_t row_prefix = hist[(size_t)tid * n_blocks + blockIdx.x];
 	{   // digit base = exclusive scan of the 256 digit totals (thread d <-> digit d) + this workgroup's row prefix
-		const uint32_t v = digit_total[tid];
-		const uint32_t incl = wave_inclusive_sum_dpp(v);
-		if (lane == 63) s_scan[wave] = incl;
-		__syncthreads();
-		const uint32_t base = (wave > 0 ? s_scan[0] : 0u) + (wave > 1 ? s_scan[1] : 0u) + (wave > 2 ? s_scan[2] : 0u) + incl - v;
-		s_off[tid] = base + row_prefix;
+		s_off[tid] = wg_exclusive_sum<BSR_VX_WAVES>(digit_total[tid], s_scan) + row_prefix;
 	}
 #pragma unroll
 	for (int w = 0; w < 4; w++) s_wcnt[w][tid] = 0u;
@@ -338,56 +318,31 @@ __global__ void __launch_bounds__(BSR_VX_BLOCK) k_voxel_heads(int E, const uint3
                                                               const uint32_t* pa, const uint64_t* kb, const uint32_t* pb,
                                                               uint32_t* __restrict__ block_heads)
 {
-	__shared__ uint32_t s_n;
+	__shared__ uint32_t s_wave[BSR_VX_WAVES];
 	if (hdr[VX_REFUSED]) return;
 	const VoxelSorted S = vx_sorted(hdr, ka, pa, kb, pb);
 	const int tid = threadIdx.x;
-	if (tid == 0) s_n = 0u;
-	__syncthreads();
 	uint32_t n = 0u;
 #pragma unroll
 	for (int k = 0; k < BSR_VX_HEAD_ROWS / BSR_VX_BLOCK; k++) {
 		const size_t i = (size_t)blockIdx.x * BSR_VX_HEAD_ROWS + k * BSR_VX_BLOCK + tid;
 		if (i < (size_t)E && (i == 0 || S.keys[i] != S.keys[i - 1])) n++;
 	}
-	const uint64_t any = wave_ballot(n != 0u);
-	if (any) {   // (uniform over the wave)
-#pragma unroll
-		for (int d = 32; d >= 1; d >>= 1) n += __shfl_xor(n, d, 64);
-		if ((tid & 63) == 0) atomicAdd(&s_n, n);   // LDS, integers
-	}
-	__syncthreads();
-	if (tid == 0) block_heads[blockIdx.x] = s_n;
+	const uint32_t heads = wg_total<BSR_VX_WAVES>(n, s_wave);
+	if (tid == 0) block_heads[blockIdx.x] = heads;
 }
 
 // ONE workgroup of 1024: block_heads[0 .. n) -> exclusive prefixes in place, in order; U = the total.
 __global__ void __launch_bounds__(1024) k_voxel_scan(int E, int n, uint32_t* hdr, uint32_t* __restrict__ block_heads,
                                                      uint32_t* __restrict__ start, uint32_t* __restrict__ status)
 {
-	__shared__ uint32_t s_wave[2][16];
-	const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+	__shared__ uint32_t s_wave[2 * 16];
+	const int tid = threadIdx.x;
 	if (hdr[VX_REFUSED]) {
 		if (tid == 0) hdr[VX_U] = status[0] = 0u;
 		return;
 	}
-	uint32_t carry = 0u;
-	int set = 0;
-	for (int base = 0; base < n; base += 1024, set ^= 1) {   // (alternating sets: one barrier per step)
-		const int i = base + tid;
-		const uint32_t v = i < n ? block_heads[i] : 0u;
-		const uint32_t incl = wave_inclusive_sum_dpp(v);
-		if (lane == 63) s_wave[set][wave] = incl;
-		__syncthreads();
-		uint32_t wave_off = 0u, total = 0u;
-#pragma unroll
-		for (int w = 0; w < 16; w++) {
-			const uint32_t t = s_wave[set][w];
-			wave_off += w < wave ? t : 0u;
-			total += t;
-		}
-		if (i < n) block_heads[i] = carry + wave_off + incl - v;
-		carry += total;
-	}
+	const uint32_t carry = wg_exclusive_scan<16, 1>(n, block_heads, s_wave, true);
 	if (tid == 0) {
 		hdr[VX_U] = status[0] = carry;
 		start[carry] = (uint32_t)E;   // the end of the last voxel (start has 3 E >= E + 1 words)
@@ -402,31 +357,22 @@ __global__ void __launch_bounds__(BSR_VX_BLOCK) k_voxel_emit(int E, const uint32
                                                              long long* __restrict__ first, T* __restrict__ points,
                                                              uint32_t* __restrict__ start)
 {
-	__shared__ uint32_t s_wave[2][4];
+	__shared__ uint32_t s_wave[2][BSR_VX_WAVES];
 	if (hdr[VX_REFUSED]) return;
 	const VoxelSorted S = vx_sorted(hdr, ka, pa, kb, pb);
 	const VoxelLayout L = voxel_layout(hdr);
-	const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-	const uint64_t lt_incl = lane == 63 ? ~0ull : ((2ull << lane) - 1ull);
+	const int tid = threadIdx.x;
 	uint32_t carry = block_heads[blockIdx.x];   // heads before this workgroup
 	for (int k = 0; k < BSR_VX_HEAD_ROWS / BSR_VX_BLOCK; k++) {
 		const size_t i = (size_t)blockIdx.x * BSR_VX_HEAD_ROWS + k * BSR_VX_BLOCK + tid;
 		const bool valid = i < (size_t)E;
 		const uint64_t key = valid ? S.keys[i] : 0ull;
 		const bool head = valid && (i == 0 || key != S.keys[i - 1]);
-		const uint64_t hb = wave_ballot(head);
-		if (lane == 0) s_wave[k & 1][wave] = (uint32_t)__popcll(hb);
-		__syncthreads();   // (set k & 1 was last read two barriers ago)
-		uint32_t before = 0u, total = 0u;
-#pragma unroll
-		for (int w = 0; w < 4; w++) {
-			const uint32_t t = s_wave[k & 1][w];
-			before += w < wave ? t : 0u;
-			total += t;
-		}
+		uint32_t total;
+		const uint32_t before = wg_exclusive_count<BSR_VX_WAVES>(head, s_wave[k & 1], total);   // (set k & 1 was last read two barriers ago)
 		if (valid) {
 			// heads up to and including this row, minus one: row 0 is a head, so the number is never negative
-			const uint32_t v = carry + before + (uint32_t)__popcll(hb & lt_incl) - 1u;
+			const uint32_t v = carry + before + (head ? 1u : 0u) - 1u;
 			const uint32_t p = S.pay[i];
 			inverse[p] = (long long)v;
 			if (head) {

@@ -61,7 +61,7 @@
  * contributes nothing to the sums and its gradient rows are written as zeros.  Gradients are always dense.
  *
  * SUMS (total, count, and the gradient of a single q).  Every thread adds its terms in fp64 in index order, a workgroup
- * adds its threads in a fixed tree, each workgroup stores one fp64 partial, and the workgroup that finishes last (an
+ * adds its threads in a fixed tree, each workgroup stores one fp64 partial per sum, and the workgroup that finishes last (an
  * integer ticket) adds the partials the same way and rounds once to fp32.  The grid is a function of (n, C, r) alone,
  * so the result is bit-identical from run to run.  Every term is an fp32 number, so with T = sum |term| and N terms
  *   |total - exact sum| <= 2^-24 |exact sum| + N 2^-53 T.
@@ -87,8 +87,8 @@ extern "C" {
 #define BSR_ENTROPY_G_DENSE 0    /* [n, C] floats, dense: the upstream of the bits output (bits times w) */
 #define BSR_ENTROPY_G_SINGLE 1   /* one float: the upstream of total */
 
-/* Bytes of scratch either call needs (a multiple of 256; 0 for an unsupported shape).  Opaque: the ticket and one fp64 and one
- * 32-bit partial per workgroup. */
+/* Bytes of scratch either call needs (a multiple of 256; 0 for an unsupported shape).  Opaque: the ticket and two fp64
+ * partials per workgroup (the sum and, as an exact integer below 2^31, the chosen rows). */
 size_t bsr_entropy_scratch_bytes(int n, int C, int r);
 
 /* The function above for every element of every chosen row.

@@ -58,6 +58,19 @@ def test_bit_equal_at_1m(kind):
         assert np.unique(x, axis=0).shape[0] < 0.96 * P   # the exact duplicates are there
 
 
+def test_bit_equal_at_257_sort_tiles():
+    """One point more than 256 sort tiles of 4096: the row scan of the sort's histogram (256 columns a step) takes a
+    second step, which is a single column and needs the carry of the first."""
+    P = 256 * 4096 + 1
+    xt = torch.from_numpy(KR.make_cloud("uniform", P, seed=1)).to(DEV)
+    got = _mean_dist3(xt)
+    ref = KR.mean_dist3_torch(xt, chunk=1024)
+    torch.cuda.synchronize()
+    g, r = got.cpu().numpy(), ref.cpu().numpy()
+    bad = np.flatnonzero(g.view(np.uint32) != r.view(np.uint32))
+    assert bad.size == 0, (bad.size, bad[:5], g[bad[:5]], r[bad[:5]])
+
+
 def test_permutation_strides_and_streams():
     P = 50_000
     x = torch.from_numpy(KR.make_cloud("surface", P, seed=4)).to(DEV)
