@@ -169,6 +169,12 @@ SIGNATURES = {
     "bsr_codec_encode_table": (C.c_int, [C.c_int] * 2 + [_F, _F, C.c_longlong, C.c_int, _F, C.c_size_t, _F, C.c_void_p,
                                                          C.c_void_p]),
     "bsr_codec_decode_table": (C.c_int, [C.c_int] * 2 + [_F, C.c_size_t, _F, C.c_longlong, _F, _F, C.c_void_p]),
+    # include/bloomscene_anchor_codec.h
+    "bsr_anchor_codec_stream_bound": (C.c_size_t, [C.c_int]),
+    "bsr_anchor_codec_scratch_bytes": (C.c_size_t, [C.c_int]),
+    "bsr_anchor_keys": (C.c_int, [C.c_int, C.c_int, _F, C.c_longlong] + [_F] * 5 + [C.c_void_p]),
+    "bsr_anchor_codec_encode": (C.c_int, [C.c_int] + [_F] * 4 + [C.c_size_t, _F, C.c_void_p, C.c_void_p]),
+    "bsr_anchor_codec_decode": (C.c_int, [C.c_int, _F, C.c_size_t] + [_F] * 4 + [C.c_void_p]),
     # include/bloomscene_adam.h (a host array of bsr_adam_tensor: AdamTensor)
     "bsr_adam_max_tensors": (C.c_int, []),
     "bsr_adam_step": (C.c_int, [C.c_int, C.POINTER(AdamTensor), C.c_double, C.c_double, C.c_double, C.c_void_p]),

@@ -274,8 +274,10 @@ def decoder_gaussian(mean, scale, Q, file_name="tmp.b", min_value=-100, max_valu
     return decode_gaussian(_read(file_name, mean.device), mean, scale, Q)
 
 
-def _bernoulli(p):
-    """[0, 1 - p, 1] per element (UE:145-149), or one row for a single p."""
+def bernoulli_cdf(p):
+    """The cdf table of a Bernoulli coder, ``[0, 1 - p, 1]`` per element of ``p`` (UE:145-149), or one row ``[3]`` for a
+    single ``p``: what ``encode_symbols`` / ``decode_symbols`` take for symbols 0 / 1 with ``p`` the probability of 1.
+    ``p = 0`` or ``1`` is legal: the symbol without mass keeps the model's floor of two counts."""
     p = p.detach().to(torch.float32).reshape(-1)
     pu = 1 - p.unsqueeze(-1)
     cdf = torch.cat([torch.zeros_like(pu), pu, torch.ones_like(pu)], dim=-1)
@@ -286,14 +288,14 @@ def encoder(x, p, file_name):
     """UE:141-157: ``x`` in {-1, +1}, ``p`` the probability of +1 (per element, or one value) -> the file's bits."""
     dev = x.device if x.device.type == "cuda" else torch.device("cuda", torch.cuda.current_device())
     sym = torch.floor((x.detach().to(dev).reshape(-1) + 1) / 2).to(torch.int16)
-    return _write(encode_symbols(sym, _bernoulli(p.to(dev))), file_name).size * 8
+    return _write(encode_symbols(sym, bernoulli_cdf(p.to(dev))), file_name).size * 8
 
 
 def decoder(p, file_name):
     """UE:159-174 -> {-1, +1} float32 on ``p``'s device."""
     dev = p.device if p.device.type == "cuda" else torch.device("cuda", torch.cuda.current_device())
     n = p.numel()
-    sym = decode_symbols(_read(file_name, dev), _bernoulli(p.to(dev)), n)
+    sym = decode_symbols(_read(file_name, dev), bernoulli_cdf(p.to(dev)), n)
     return (sym * 2 - 1).to(torch.float32).to(p.device)
 
 

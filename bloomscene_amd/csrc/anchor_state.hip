@@ -22,6 +22,7 @@
 #include "common.h"
 #include "mlp_rows.h"
 #include "wg_scan.h"
+#include "anchor_lattice.h"
 #include "../../include/bloomscene_anchor_state.h"
 
 namespace bsr {
@@ -32,29 +33,7 @@ namespace bsr {
 #define AST_SCAN BSR_ANCHOR_STATE_SCAN
 #define AST_ROUNDS (AST_SCAN / AST_BLOCK)
 
-// torch.div(a, b, rounding_mode='floor') on fp32, operation for operation (the header writes it out)
-__device__ __forceinline__ float floor_div(float a, float b)
-{
-	if (b == 0.0f) return a / b;
-	const float mod = fmodf(a, b);
-	float div = (a - mod) / b;
-	if (mod != 0.0f && (b < 0.0f) != (mod < 0.0f)) div = div - 1.0f;
-	if (div != 0.0f) {
-		float q = floorf(div);
-		if (div - q > 0.5f) q = q + 1.0f;
-		return q;
-	}
-	return copysignf(0.0f, a / b);
-}
-
-__device__ __forceinline__ float quantize_anchor(float x, float lo, float hi)
-{
-	const float interval = ((hi - lo) * (float)(1.0 / 65535.0)) + 1e-6f;
-	float q = floor_div(x - lo, interval);
-	q = q < 0.0f ? 0.0f : (q > 65535.0f ? 65535.0f : q);
-	return q * interval + lo;
-}
-
+// (quantize_anchor, rule A of the header: anchor_lattice.h, shared with the position coder)
 __device__ __forceinline__ float mask_decision(float x) { return heads_sigmoid(x) > 0.01f ? 1.0f : 0.0f; }
 
 enum { AST_COPY, AST_ANCHOR, AST_EXP, AST_MASK };
