@@ -190,6 +190,13 @@ SIGNATURES = {
                           + [_F] * 4 + [C.c_void_p, C.c_void_p]),
     "bsr_resize_max_tensors": (C.c_int, []),
     "bsr_rows_resize": (C.c_int, [C.c_int, C.POINTER(ResizeTensor), C.c_int, C.c_int, C.c_int, _F, C.c_void_p]),
+    # include/bloomscene_reproject.h (a host array of 21 doubles: the camera)
+    "bsr_reproject_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int]),
+    "bsr_warp_points": (C.c_int, [C.c_int] * 3 + [_F, C.c_longlong, C.c_longlong, _F, C.POINTER(C.c_double), C.c_int, C.c_double]
+                        + [_F] * 6 + [C.c_void_p]),
+    "bsr_lift_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int]),
+    "bsr_lift_count": (C.c_int, [C.c_int, C.c_int, _F, _F, _F, C.c_void_p]),
+    "bsr_lift_pixels": (C.c_int, [C.c_int, C.c_int, _F, _F, _F, C.POINTER(C.c_double), _F, _F, C.c_int, _F, _F, C.c_void_p]),
 }
 
 HeadsPointers = C.c_void_p * 12   # bsr_heads_weights / bsr_heads_weight_grads: (w1, b1, w2, b2) of opacity, cov, color
