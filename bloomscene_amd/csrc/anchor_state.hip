@@ -34,7 +34,7 @@ namespace bsr {
 #define AST_ROUNDS (AST_SCAN / AST_BLOCK)
 
 // (quantize_anchor, rule A of the header: anchor_lattice.h, shared with the position coder)
-__device__ __forceinline__ float mask_decision(float x) { return heads_sigmoid(x) > 0.01f ? 1.0f : 0.0f; }
+__device__ __forceinline__ float mask_decision(float x) { return mlp_sigmoid(x) > 0.01f ? 1.0f : 0.0f; }
 
 enum { AST_COPY, AST_ANCHOR, AST_EXP, AST_MASK };
 
@@ -121,7 +121,7 @@ __device__ __forceinline__ void scatter_rows(const float* __restrict__ g, int C,
 			v = g[i * C + c];
 			if (Op == AST_G_EXP) v = v * aux[i * C + c];
 			if (Op == AST_G_MASK) {
-				const float s = heads_sigmoid(aux[(size_t)(r0 + j) * C + c]);
+				const float s = mlp_sigmoid(aux[(size_t)(r0 + j) * C + c]);
 				v = (v * s) * (1.0f - s);
 			}
 		}

@@ -6,8 +6,7 @@
 //   k_context_quantise   enc -> hid -> the last three rows of layer 2 -> Q -> the quantised attributes
 //   k_context_bwd_rows   recomputes hid and the adjustments, forms dpre2 / dpre1 / d enc per row; with a weight gradient
 //                        asked for it also leaves enc, hid, dpre1, dpre2 of every row in the scratch
-//   k_context_wgrad      per range of BSR_CONTEXT_CHUNK rows one partial of every weight-gradient element
-//   k_context_wsum       adds the partials of an element in ascending range order
+//   k_mlp_wgrad, k_mlp_wsum (mlp_wgrad.h)   the weight gradients from that scratch: context_segments, context_products
 //
 // The lane mapping and the products are those of mlp_rows.h (a lane per row, 64 rows per workgroup, [index][lane] planes
 // in LDS, 8 x 8 weights per vector load); unlike the heads' one wave, a workgroup here is several waves that share the
@@ -16,11 +15,11 @@
 // out of their blocks on the way.  The elementwise tails run
 // cooperatively (consecutive lanes on consecutive elements of a row) with the row's Q read from LDS.  The row pass holds
 // enc, hid and one plane per column of dpre2 -- 129 KB at the limits -- and reuses the planes: g_out / noise are staged
-// in dpre2's before g_context is, hid turns into dpre1 in place, and d enc is formed in enc's.  The weight-gradient sums
-// are k_heads_wgrad's scheme for one stack.
-#include <atomic>
+// in dpre2's before g_context is, hid turns into dpre1 in place, and d enc is formed in enc's.
 #include "common.h"
+#include "lds_reserve.h"
 #include "mlp_rows.h"
+#include "mlp_wgrad.h"
 #include "../../include/bloomscene_context.h"
 
 namespace bsr {
@@ -28,7 +27,6 @@ namespace bsr {
 #define CTX_T MLP_ROWS_T
 #define CTX_P MLP_ROWS_P
 #define CTX_NJ MLP_ROWS_NJ
-#define CTX_SUM_BLOCK 256
 // Waves of a workgroup.  They share the 64 rows and their planes in LDS and split the blocks of eight outputs of every
 // product among them: LDS, not registers, limits how many workgroups a CU holds (one of the row pass at BloomScene's
 // shape), and a lone wave per SIMD cannot hide its own LDS and weight-load latencies.
@@ -54,35 +52,33 @@ struct ContextTail {
 	const float* mean[3];
 };
 
-struct ContextRowScratch {
-	float *x, *hid, *dp1, *dp2;
-	size_t ldx, ldh, ld2;
-};
-
-struct ContextLayout {
-	size_t ldx, ldh, ld2;       // row pitches (floats) of enc [D], hid / dp1 [H], dp2 [O]: a multiple of 4, + 4
-	size_t chunks;              // ranges of BSR_CONTEXT_CHUNK rows
-	int tot;                    // weight-gradient elements: W1, b1, W2, b2
-	size_t off_hid, off_dp1, off_dp2, off_partials, floats;
-};
-
 static int context_outputs(int F, int K) { return 2 * F + 12 + 6 * K + 3; }
 
-static ContextLayout context_layout(int n, int D, int H, int F, int K)
+// Element order of a partial: W1 [H, D], b1 [H], W2 [O, H], b2 [O].
+static MlpSegments context_segments(int D, int H, int O, const bsr_context_weight_grads* dw)
 {
-	const size_t O = (size_t)context_outputs(F, K);
-	ContextLayout l;
-	l.ldx = (((size_t)D + 3) & ~(size_t)3) + 4;
-	l.ldh = (((size_t)H + 3) & ~(size_t)3) + 4;
-	l.ld2 = ((O + 3) & ~(size_t)3) + 4;
-	l.chunks = ((size_t)n + BSR_CONTEXT_CHUNK - 1) / BSR_CONTEXT_CHUNK;
-	l.tot = H * D + H + (int)O * H + (int)O;
-	l.off_hid = (size_t)n * l.ldx;
-	l.off_dp1 = l.off_hid + (size_t)n * l.ldh;
-	l.off_dp2 = l.off_dp1 + (size_t)n * l.ldh;
-	l.off_partials = l.off_dp2 + (size_t)n * l.ld2;
-	l.floats = l.off_partials + l.chunks * (size_t)l.tot + 64;
-	return l;
+	const bsr_context_weight_grads g = dw ? *dw : bsr_context_weight_grads{};
+	MlpSegments d = {};
+	d.add(H * D, g.w1);
+	d.add(H, g.b1);
+	d.add(O * H, g.w2);
+	d.add(O, g.b2);
+	return d;
+}
+
+static MlpProducts context_products(int D, int H, int O, const MlpRowScratch& rs, const MlpSegments& d)
+{
+	MlpProducts p = {};
+	p.add(rs.dp1, rs.ldh, rs.x, rs.ldx, H, D, d, 0, 1);
+	p.add(rs.dp2, rs.ld2, rs.hid, rs.ldh, O, H, d, 2, 3);
+	return p;
+}
+
+// enc [D], hid / dp1 [H], dp2 [O]
+static MlpWgradLayout context_layout(int n, int D, int H, int F, int K)
+{
+	const int O = context_outputs(F, K);
+	return mlp_wgrad_layout(n, D, H, O, context_segments(D, H, O, nullptr).tot);
 }
 
 static bool context_shape_ok(int n, int D, int H, int F, int K)
@@ -132,7 +128,7 @@ __device__ __forceinline__ void hidden_layer(const ContextArgs& a, const float* 
 		for (int jj = 0; jj < CTX_NJ; jj++)
 			if (j0 + jj < a.H) {
 				if (pre1) pre1[j0 + jj] = acc[jj];
-				Hs[(j0 + jj) * CTX_P + t.lane] = heads_relu(acc[jj]);
+				Hs[(j0 + jj) * CTX_P + t.lane] = mlp_relu(acc[jj]);
 			}
 	}
 }
@@ -148,7 +144,7 @@ __device__ __forceinline__ void adjustments(const ContextArgs& a, const float* H
 	adj[2] = acc[2];
 }
 
-__device__ __forceinline__ float step_size(float q, float adj) { return q * (1.0f + heads_tanh(adj)); }
+__device__ __forceinline__ float step_size(float q, float adj) { return q * (1.0f + mlp_tanh(adj)); }
 
 __global__ void __launch_bounds__(CTX_MAX_THREADS) k_context_fwd(ContextArgs a, ContextTail t, float* __restrict__ context,
                                                                  float* __restrict__ Q, float* __restrict__ maps)
@@ -243,7 +239,7 @@ __global__ void __launch_bounds__(CTX_MAX_THREADS) k_context_quantise(ContextArg
 			x = x < lo ? lo : x;
 			x = x > hi ? hi : x;
 			const float qq = rintf(x / q) * q;
-			dst[idx] = qq + heads_tanh(x - qq) * q;
+			dst[idx] = qq + mlp_tanh(x - qq) * q;
 		}
 	}
 }
@@ -255,7 +251,7 @@ struct ContextUpstreams {
 };
 
 __global__ void __launch_bounds__(CTX_MAX_THREADS) k_context_bwd_rows(ContextArgs a, ContextUpstreams u, float* __restrict__ d_enc,
-                                                                      ContextRowScratch rs)
+                                                                      MlpRowScratch rs)
 {
 	extern __shared__ float ctx_lds[];
 	const ContextThread th = context_thread();
@@ -300,7 +296,7 @@ __global__ void __launch_bounds__(CTX_MAX_THREADS) k_context_bwd_rows(ContextArg
 			adjustments(a, Hs, adj, lane);
 #pragma unroll
 			for (int c = 0; c < 3; c++) {
-				const float tn = heads_tanh(adj[c]);
+				const float tn = mlp_tanh(adj[c]);
 				dadj[c] = (dq[c] * a.q[c]) * (1.0f - tn * tn);
 			}
 		}
@@ -337,93 +333,6 @@ __global__ void __launch_bounds__(CTX_MAX_THREADS) k_context_bwd_rows(ContextArg
 	}
 	__syncthreads();
 	coop_store(d_enc + (size_t)row0 * D, (size_t)D, D, Xs, rows, th.tid, th.threads);
-}
-
-struct ContextSumArgs {
-	int n, D, H, O, tot;
-	const float *x, *hid, *dp1, *dp2;
-	size_t ldx, ldh, ld2;
-	float* partials;
-};
-
-// Element order of a partial (and of k_context_wsum): W1 [H, D], b1 [H], W2 [O, H], b2 [O].  A thread owns a 4 x 4 block
-// of one weight matrix (and, in the first column of blocks, four bias elements).
-__global__ void __launch_bounds__(CTX_SUM_BLOCK) k_context_wgrad(ContextSumArgs s)
-{
-	const int D = s.D, H = s.H, O = s.O;
-	int u = blockIdx.y * CTX_SUM_BLOCK + threadIdx.x;
-	const int KB1 = (D + 3) >> 2, JB1 = (H + 3) >> 2, KB2 = (H + 3) >> 2, JB2 = (O + 3) >> 2;
-	const float *A, *B;
-	size_t lda, ldb;
-	int jv, kv, out, outld, bout, kb;
-	if (u < JB1 * KB1) {
-		const int jb = u / KB1;
-		kb = u - jb * KB1;
-		A = s.dp1 + 4 * jb; lda = s.ldh;
-		B = s.x + 4 * kb; ldb = s.ldx;
-		jv = H - 4 * jb; kv = D - 4 * kb;
-		out = 4 * jb * D + 4 * kb; outld = D;
-		bout = H * D + 4 * jb;
-	} else {
-		u -= JB1 * KB1;
-		if (u >= JB2 * KB2) return;
-		const int jb = u / KB2;
-		kb = u - jb * KB2;
-		A = s.dp2 + 4 * jb; lda = s.ld2;
-		B = s.hid + 4 * kb; ldb = s.ldh;
-		jv = O - 4 * jb; kv = H - 4 * kb;
-		out = H * D + H + 4 * jb * H + 4 * kb; outld = H;
-		bout = H * D + H + O * H + 4 * jb;
-	}
-	const size_t r0 = (size_t)blockIdx.x * BSR_CONTEXT_CHUNK;
-	const size_t r1 = r0 + BSR_CONTEXT_CHUNK < (size_t)s.n ? r0 + BSR_CONTEXT_CHUNK : (size_t)s.n;
-	// fp64: a product of two fp32 values is exact there, so a range's sum is rounded once, when it is stored
-	double acc[4][4], ab[4];
-#pragma unroll
-	for (int jj = 0; jj < 4; jj++) {
-		ab[jj] = 0.0;
-#pragma unroll
-		for (int kk = 0; kk < 4; kk++) acc[jj][kk] = 0.0;
-	}
-	for (size_t r = r0; r < r1; r++) {
-		const bsr_f32x4 av = *reinterpret_cast<const bsr_f32x4_a4*>(A + r * lda);
-		const bsr_f32x4 bv = *reinterpret_cast<const bsr_f32x4_a4*>(B + r * ldb);
-		const double aa[4] = {(double)av.x, (double)av.y, (double)av.z, (double)av.w};
-		const double bb[4] = {(double)bv.x, (double)bv.y, (double)bv.z, (double)bv.w};
-#pragma unroll
-		for (int jj = 0; jj < 4; jj++) {
-			ab[jj] = ab[jj] + aa[jj];
-#pragma unroll
-			for (int kk = 0; kk < 4; kk++) acc[jj][kk] = fma(aa[jj], bb[kk], acc[jj][kk]);
-		}
-	}
-	float* P = s.partials + (size_t)blockIdx.x * s.tot;
-#pragma unroll
-	for (int jj = 0; jj < 4; jj++) {
-		if (jj >= jv) continue;
-#pragma unroll
-		for (int kk = 0; kk < 4; kk++)
-			if (kk < kv) P[out + jj * outld + kk] = (float)acc[jj][kk];
-		if (kb == 0) P[bout + jj] = (float)ab[jj];
-	}
-}
-
-__global__ void __launch_bounds__(CTX_SUM_BLOCK) k_context_wsum(const float* __restrict__ partials, size_t chunks, int tot, int D,
-                                                                int H, int O, bsr_context_weight_grads dw)
-{
-	int t = blockIdx.x * CTX_SUM_BLOCK + threadIdx.x;
-	if (t >= tot) return;
-	double sum = (double)partials[t];
-	for (size_t c = 1; c < chunks; c++) sum = sum + (double)partials[c * (size_t)tot + t];
-	float* p;
-	if (t < H * D) p = dw.w1;
-	else if ((t -= H * D) < H) p = dw.b1;
-	else if ((t -= H) < O * H) p = dw.w2;
-	else {
-		t -= O * H;
-		p = dw.b2;
-	}
-	if (p) p[t] = (float)sum;
 }
 
 // the checks the entry points share; fills the arguments
@@ -465,36 +374,6 @@ static int context_attribute(const char* who, const char* name, int C, const flo
 	return 0;
 }
 
-// A workgroup's LDS is dynamic: refuse what the device cannot give one workgroup, and ask for more than the default
-// 64 KiB once per kernel and DEVICE (not per call).  Two host threads that meet here both ask, which is harmless: the
-// state is atomic and both store the same answer.
-#define CTX_MAX_DEVICES 64
-template <typename Kern>
-static int context_lds(const char* who, Kern kern, size_t bytes)
-{
-	static std::atomic<int> device_lds[CTX_MAX_DEVICES];   // 0 not asked yet, else the device's LDS bytes per workgroup
-	static std::atomic<int> state[CTX_MAX_DEVICES];        // (one array per kernel type) 0 not asked yet, 1 granted, -1 refused
-	int dev = 0;
-	if (hipGetDevice(&dev) != hipSuccess || dev < 0) return fail("%s: no current device", who);
-	const bool tracked = dev < CTX_MAX_DEVICES;
-	int have = tracked ? device_lds[dev].load(std::memory_order_relaxed) : 0;
-	if (have == 0) {
-		if (hipDeviceGetAttribute(&have, hipDeviceAttributeMaxSharedMemoryPerBlock, dev) != hipSuccess || have <= 0)
-			return fail("%s: cannot read the device's LDS size", who);
-		if (tracked) device_lds[dev].store(have, std::memory_order_relaxed);
-	}
-	if (bytes > (size_t)have)
-		return fail("%s: a workgroup needs %zu bytes of LDS, the device gives one %d", who, bytes, have);
-	if (bytes <= 64 * 1024) return 0;
-	int st = tracked ? state[dev].load(std::memory_order_relaxed) : 0;
-	if (st == 0) {
-		st = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, have) == hipSuccess ? 1 : -1;
-		if (tracked) state[dev].store(st, std::memory_order_relaxed);
-	}
-	if (st < 0) return fail("%s: cannot reserve %zu bytes of LDS", who, bytes);
-	return 0;
-}
-
 static unsigned context_blocks(int n) { return (unsigned)(((long long)n + CTX_T - 1) / CTX_T); }
 
 }  // namespace bsr
@@ -528,7 +407,7 @@ int bsr_context_head_forward(int n, int D, int H, int F, int K, const float* enc
 	ContextTail t = {{feat, scaling, offsets}, {feat_stride, scaling_stride, offsets_stride},
 	                 {noise_feat, noise_scaling, noise_offsets}, {out_feat, out_scaling, out_offsets}, {nullptr, nullptr, nullptr}};
 	const size_t lds = (size_t)(D + H + 3) * CTX_P * sizeof(float);
-	if (context_lds(who, k_context_fwd, lds)) return 1;
+	if (reserve_lds<k_context_fwd>(who, lds)) return 1;
 	hipLaunchKernelGGL(k_context_fwd, dim3(context_blocks(n)), dim3(CTX_T * CTX_FWD_WAVES), lds, (hipStream_t)stream, a, t, context, Q, maps);
 	if (hipGetLastError() != hipSuccess) return fail("%s: launch failed", who);
 	return 0;
@@ -552,7 +431,7 @@ int bsr_context_quantise_forward(int n, int D, int H, int F, int K, const float*
 	ContextTail t = {{feat, scaling, offsets}, {feat_stride, scaling_stride, offsets_stride}, {nullptr, nullptr, nullptr},
 	                 {out_feat, out_scaling, out_offsets}, {feat_mean, scaling_mean, offsets_mean}};
 	const size_t lds = (size_t)(D + H + 3) * CTX_P * sizeof(float);
-	if (context_lds(who, k_context_quantise, lds)) return 1;
+	if (reserve_lds<k_context_quantise>(who, lds)) return 1;
 	hipLaunchKernelGGL(k_context_quantise, dim3(context_blocks(n)), dim3(CTX_T * CTX_FWD_WAVES), lds, (hipStream_t)stream, a, t, Q);
 	if (hipGetLastError() != hipSuccess) return fail("%s: launch failed", who);
 	return 0;
@@ -576,47 +455,20 @@ int bsr_context_head_backward(int n, int D, int H, int F, int K, const float* en
 		bits |= (uintptr_t)u.g_out[c] | (uintptr_t)u.noise[c];
 	}
 	if (bits & 3) return fail("%s: upstreams and gradients must be 4-byte aligned", who);
-	bsr_context_weight_grads grads = {};
-	if (dw) grads = *dw;
-	const bool sums = grads.w1 || grads.b1 || grads.w2 || grads.b2;
-	if (((uintptr_t)grads.w1 | (uintptr_t)grads.b1 | (uintptr_t)grads.w2 | (uintptr_t)grads.b2) & 3)
-		return fail("%s: weight gradients must be 4-byte aligned", who);
+	const MlpSegments grads = context_segments(D, H, a.O, dw);
+	if (mlp_wgrad_check(who, grads)) return 1;
+	const bool sums = mlp_wgrad_asked(grads);
 	hipStream_t st = (hipStream_t)stream;
-	const size_t O = (size_t)a.O;
-	if (n == 0) {
-		float* p[4] = {grads.w1, grads.b1, grads.w2, grads.b2};
-		const size_t count[4] = {(size_t)H * D, (size_t)H, O * H, O};
-		for (int i = 0; i < 4; i++)
-			if (p[i] && hipMemsetAsync(p[i], 0, count[i] * sizeof(float), st) != hipSuccess) return fail("%s: memset failed", who);
-		return 0;
-	}
-	if (sums && !scratch) return fail("%s: the weight gradients need the scratch", who);
-	if ((uintptr_t)scratch & 15) return fail("%s: scratch must be 16-byte aligned", who);
-	const ContextLayout l = context_layout(n, D, H, F, K);
-	ContextRowScratch rs = {};
-	float* base = (float*)scratch;
-	if (sums) {
-		rs.x = base; rs.hid = base + l.off_hid; rs.dp1 = base + l.off_dp1; rs.dp2 = base + l.off_dp2;
-		rs.ldx = l.ldx; rs.ldh = l.ldh; rs.ld2 = l.ld2;
-	}
-	const size_t lds = ((size_t)D + H + O) * CTX_P * sizeof(float);
-	if (context_lds(who, k_context_bwd_rows, lds)) return 1;
+	if (n == 0) return mlp_wgrad_zero(who, grads, st);
+	const MlpWgradLayout l = context_layout(n, D, H, F, K);
+	MlpRowScratch rs;
+	if (mlp_wgrad_carve(who, l, sums, scratch, rs)) return 1;
+	const size_t lds = ((size_t)D + H + a.O) * CTX_P * sizeof(float);
+	if (reserve_lds<k_context_bwd_rows>(who, lds)) return 1;
 	hipLaunchKernelGGL(k_context_bwd_rows, dim3(context_blocks(n)), dim3(CTX_T * CTX_BWD_WAVES), lds, st, a, u, d_enc, rs);
 	if (hipGetLastError() != hipSuccess) return fail("%s: launch failed", who);
 	if (!sums) return 0;
-	ContextSumArgs s;
-	s.n = n; s.D = D; s.H = H; s.O = a.O; s.tot = l.tot;
-	s.x = rs.x; s.hid = rs.hid; s.dp1 = rs.dp1; s.dp2 = rs.dp2;
-	s.ldx = l.ldx; s.ldh = l.ldh; s.ld2 = l.ld2;
-	s.partials = base + l.off_partials;
-	const int units = ((H + 3) / 4) * ((D + 3) / 4) + ((a.O + 3) / 4) * ((H + 3) / 4);
-	hipLaunchKernelGGL(k_context_wgrad, dim3((unsigned)l.chunks, (unsigned)((units + CTX_SUM_BLOCK - 1) / CTX_SUM_BLOCK)),
-	                   dim3(CTX_SUM_BLOCK), 0, st, s);
-	if (hipGetLastError() != hipSuccess) return fail("%s: launch failed", who);
-	hipLaunchKernelGGL(k_context_wsum, dim3((unsigned)((l.tot + CTX_SUM_BLOCK - 1) / CTX_SUM_BLOCK)), dim3(CTX_SUM_BLOCK), 0, st,
-	                   s.partials, l.chunks, l.tot, D, H, a.O, grads);
-	if (hipGetLastError() != hipSuccess) return fail("%s: launch failed", who);
-	return 0;
+	return mlp_wgrad_sums(who, context_products(D, H, a.O, rs, grads), grads, n, l, scratch, st);
 }
 
 }  // extern "C"

@@ -4,8 +4,7 @@
 //   k_heads_fwd        X -> hid -> pre2 -> the three outputs, one head after the other
 //   k_heads_bwd_rows   recomputes hid, forms dpre2 / dpre1 / dX per row -> d feat, d anchor, d offset_mask; with a weight
 //                      gradient asked for it also leaves X, hid, dpre1, dpre2 of every row in the scratch
-//   k_heads_wgrad      per range of BSR_HEADS_CHUNK rows one partial of every weight-gradient element
-//   k_heads_wsum       adds the partials of an element in ascending range order
+//   k_mlp_wgrad, k_mlp_wsum (mlp_wgrad.h)   the weight gradients from that scratch: heads_segments, heads_products
 //
 // LANE MAPPING (forward and row pass).  A lane is an anchor row; a workgroup is ONE wave of 64 rows.  The row's vectors
 // that are indexed by a loop variable (X, hid, dpre2, dX) live in LDS as [index][lane] with a pitch of 65 floats: the
@@ -15,13 +14,14 @@
 // of it as a scalar operand (mlp_rows.h, which holds these products: THE WEIGHTS OF A STEP), with one LDS read per eight
 // FMAs.  Every chain is written with explicit fmaf in the order the header states: the build stays at -ffp-contract=off.
 // WEIGHT GRADIENTS.  The reduction index is the row, which the row pass has on the lane; so that pass stores its per-row
-// operands (row-major, rows padded to 16 bytes) and k_heads_wgrad runs dW = dpre^T X as a register-blocked product: a
+// operands (row-major, rows padded to 16 bytes) and k_mlp_wgrad runs dW = dpre^T X as a register-blocked product: a
 // thread owns a 4 x 4 block of one weight matrix and walks its range of rows in order, two 16-byte loads per 16 FMAs
 // (fp64 ones: the sums over rows are the one place where fp32 accumulation in a fixed order loses to a library's tree).
 // The grid is a function of (n, F, K) alone.
-#include <atomic>
 #include "common.h"
-#include "mlp_rows.h"   // uload, lane_value, step_fma, chain_rows, dot_cols, coop_store, store_block, the activations
+#include "lds_reserve.h"
+#include "mlp_rows.h"   // uload, lane_value, step_fma, chain_rows, dot_cols, coop_store, coop_zero, store_block, the activations
+#include "mlp_wgrad.h"
 #include "../../include/bloomscene_heads.h"
 
 namespace bsr {
@@ -29,7 +29,6 @@ namespace bsr {
 #define HEADS_T MLP_ROWS_T     // rows a workgroup (one wave)
 #define HEADS_P MLP_ROWS_P     // LDS pitch of a [index][lane] vector
 #define HEADS_NJ MLP_ROWS_NJ   // outputs accumulated at a time
-#define HEADS_SUM_BLOCK 256
 
 struct HeadsArgs {
 	int n, F, K;
@@ -39,34 +38,33 @@ struct HeadsArgs {
 	bsr_heads_weights w;
 };
 
-// what the row pass leaves for the weight-gradient sums (all NULL: nothing is left)
-struct HeadsRowScratch {
-	float *x, *hid, *dp1, *dp2;
-	size_t ldx, ldh, ld2;
-};
+__host__ __device__ __forceinline__ int heads_outputs(int h, int K) { return h == 0 ? K : (h == 1 ? 7 * K : 3 * K); }
+__host__ __device__ __forceinline__ int heads_offset(int h, int K) { return h == 0 ? 0 : (h == 1 ? K : 8 * K); }
 
-struct HeadsLayout {
-	size_t ldx, ldh, ld2;       // row pitches (floats) of x [F + 4], hid / dp1 [3 F], dp2 [11 K]: a multiple of 4, + 4
-	size_t chunks;              // ranges of BSR_HEADS_CHUNK rows
-	int tot;                    // weight-gradient elements: W1 (3 heads), b1, W2, b2
-	size_t off_hid, off_dp1, off_dp2, off_partials, floats;
-};
-
-static HeadsLayout heads_layout(int n, int F, int K)
+// Element order of a partial: W1 of the three heads [3 F, F + 4], b1 [3 F], W2 [11 K, F], b2 [11 K], each cut by head.
+static MlpSegments heads_segments(int F, int K, const bsr_heads_weight_grads* dw)
 {
-	HeadsLayout l;
-	l.ldx = (((size_t)F + 4 + 3) & ~(size_t)3) + 4;
-	l.ldh = ((3 * (size_t)F + 3) & ~(size_t)3) + 4;
-	l.ld2 = ((11 * (size_t)K + 3) & ~(size_t)3) + 4;
-	l.chunks = ((size_t)n + BSR_HEADS_CHUNK - 1) / BSR_HEADS_CHUNK;
-	l.tot = 3 * F * (F + 4) + 3 * F + 11 * K * F + 11 * K;
-	l.off_hid = (size_t)n * l.ldx;
-	l.off_dp1 = l.off_hid + (size_t)n * l.ldh;
-	l.off_dp2 = l.off_dp1 + (size_t)n * l.ldh;
-	l.off_partials = l.off_dp2 + (size_t)n * l.ld2;
-	l.floats = l.off_partials + l.chunks * (size_t)l.tot + 64;
-	return l;
+	const bsr_heads_weight_grads g = dw ? *dw : bsr_heads_weight_grads{};
+	MlpSegments d = {};
+	for (int h = 0; h < 3; h++) d.add(F * (F + 4), g.head[h].w1);
+	for (int h = 0; h < 3; h++) d.add(F, g.head[h].b1);
+	for (int h = 0; h < 3; h++) d.add(heads_outputs(h, K) * F, g.head[h].w2);
+	for (int h = 0; h < 3; h++) d.add(heads_outputs(h, K), g.head[h].b2);
+	return d;
 }
+
+// layer 1 of the three heads as ONE stacked product over the shared X, layer 2 head by head
+static MlpProducts heads_products(int F, int K, const MlpRowScratch& rs, const MlpSegments& d)
+{
+	MlpProducts p = {};
+	p.add(rs.dp1, rs.ldh, rs.x, rs.ldx, 3 * F, F + 4, d, 0, 3);
+	for (int h = 0; h < 3; h++)
+		p.add(rs.dp2 + heads_offset(h, K), rs.ld2, rs.hid + h * F, rs.ldh, heads_outputs(h, K), F, d, 6 + h, 9 + h);
+	return p;
+}
+
+// x [F + 4], hid / dp1 [3 F], dp2 [11 K]
+static MlpWgradLayout heads_layout(int n, int F, int K) { return mlp_wgrad_layout(n, F + 4, 3 * F, 11 * K, heads_segments(F, K, nullptr).tot); }
 
 static bool heads_shape_ok(int n, int F, int K)
 {
@@ -99,17 +97,6 @@ __device__ __forceinline__ void stage_x(const HeadsArgs& a, float* Xs, long long
 	Xs[(F + 3) * HEADS_P + lane] = dist;
 }
 
-__device__ __forceinline__ void coop_zero(float* dst, size_t ld, int C, int rows, int lane)
-{
-	for (int idx = lane; idx < rows * C; idx += HEADS_T) {
-		const int r = idx / C, c = idx - r * C;
-		dst[(size_t)r * ld + c] = 0.0f;
-	}
-}
-
-__device__ __forceinline__ int heads_outputs(int h, int K) { return h == 0 ? K : (h == 1 ? 7 * K : 3 * K); }
-__device__ __forceinline__ int heads_offset(int h, int K) { return h == 0 ? 0 : (h == 1 ? K : 8 * K); }
-
 __global__ void __launch_bounds__(HEADS_T) k_heads_fwd(HeadsArgs a, float* __restrict__ opacity, float* __restrict__ color,
                                                        float* __restrict__ scale_rot, float* __restrict__ maps)
 {
@@ -135,7 +122,7 @@ __global__ void __launch_bounds__(HEADS_T) k_heads_fwd(HeadsArgs a, float* __res
 			for (int jj = 0; jj < HEADS_NJ; jj++)
 				if (j0 + jj < F) {
 					if (maps && valid) pre1[h * F + j0 + jj] = acc[jj];
-					Hs[(j0 + jj) * HEADS_P + lane] = heads_relu(acc[jj]);
+					Hs[(j0 + jj) * HEADS_P + lane] = mlp_relu(acc[jj]);
 				}
 		}
 		__syncthreads();
@@ -152,12 +139,12 @@ __global__ void __launch_bounds__(HEADS_T) k_heads_fwd(HeadsArgs a, float* __res
 			if (h == 0) {
 #pragma unroll
 				for (int jj = 0; jj < HEADS_NJ; jj++) {
-					const float t = heads_tanh(acc[jj]);
+					const float t = mlp_tanh(acc[jj]);
 					acc[jj] = a.mask && jj < count ? t * a.mask[(size_t)row * K + o0 + jj] : t;
 				}
 			} else if (h == 2) {
 #pragma unroll
-				for (int jj = 0; jj < HEADS_NJ; jj++) acc[jj] = heads_sigmoid(acc[jj]);
+				for (int jj = 0; jj < HEADS_NJ; jj++) acc[jj] = mlp_sigmoid(acc[jj]);
 			}
 			store_block(out + o0, acc, count);
 		}
@@ -169,7 +156,7 @@ __global__ void __launch_bounds__(HEADS_T) k_heads_bwd_rows(HeadsArgs a, const f
                                                             const float* __restrict__ g_o, const float* __restrict__ g_c,
                                                             const float* __restrict__ g_s, float* __restrict__ d_feat,
                                                             float* __restrict__ d_anchor, float* __restrict__ d_mask,
-                                                            HeadsRowScratch rs)
+                                                            MlpRowScratch rs)
 {
 	extern __shared__ float heads_lds[];
 	const int F = a.F, K = a.K, Kd = F + 4, lane = threadIdx.x;
@@ -205,7 +192,7 @@ __global__ void __launch_bounds__(HEADS_T) k_heads_bwd_rows(HeadsArgs a, const f
 			chain_rows(w1, b1, F, Kd, j0, Xs + lane, acc, lane);
 #pragma unroll
 			for (int jj = 0; jj < HEADS_NJ; jj++)
-				if (j0 + jj < F) Hs[(j0 + jj) * HEADS_P + lane] = heads_relu(acc[jj]);
+				if (j0 + jj < F) Hs[(j0 + jj) * HEADS_P + lane] = mlp_relu(acc[jj]);
 		}
 		__syncthreads();
 		if (sums) coop_store(rs.hid + (size_t)row0 * rs.ldh + h * F, rs.ldh, F, Hs, rows, lane);
@@ -216,7 +203,7 @@ __global__ void __launch_bounds__(HEADS_T) k_heads_bwd_rows(HeadsArgs a, const f
 				for (int jj = 0; jj < HEADS_NJ; jj++) {
 					const int o = o0 + jj;
 					if (o < O) {
-						const float t = heads_tanh(acc[jj]);
+						const float t = mlp_tanh(acc[jj]);
 						const float m = a.mask && valid ? a.mask[(size_t)row * K + o] : 1.0f;
 						const float go = valid ? g[(size_t)row * K + o] : 0.0f;
 						if (d_mask && valid) d_mask[(size_t)row * K + o] = go * t;
@@ -281,114 +268,6 @@ __global__ void __launch_bounds__(HEADS_T) k_heads_bwd_rows(HeadsArgs a, const f
 	}
 }
 
-struct HeadsSumArgs {
-	int n, F, K, tot;
-	const float *x, *hid, *dp1, *dp2;
-	size_t ldx, ldh, ld2;
-	float* partials;
-};
-
-// Element order of a partial (and of k_heads_wsum): W1 of the three heads [3 F, F + 4], b1 [3 F], W2 [11 K, F], b2 [11 K].
-__global__ void __launch_bounds__(HEADS_SUM_BLOCK) k_heads_wgrad(HeadsSumArgs s)
-{
-	const int F = s.F, K = s.K, Kd = F + 4;
-	int u = blockIdx.y * HEADS_SUM_BLOCK + threadIdx.x;
-	const int KB0 = (Kd + 3) >> 2, JB0 = (3 * F + 3) >> 2, KB = (F + 3) >> 2;
-	const float *A, *B;
-	size_t lda, ldb;
-	int jv, kv, out, outld, bout, kb;
-	if (u < JB0 * KB0) {
-		const int jb = u / KB0;
-		kb = u - jb * KB0;
-		A = s.dp1 + 4 * jb; lda = s.ldh;
-		B = s.x + 4 * kb; ldb = s.ldx;
-		jv = 3 * F - 4 * jb; kv = Kd - 4 * kb;
-		out = 4 * jb * Kd + 4 * kb; outld = Kd;
-		bout = 3 * F * Kd + 4 * jb;
-	} else {
-		u -= JB0 * KB0;
-		int h = 0, off = 0, O = K;
-		for (; h < 3; h++) {
-			O = heads_outputs(h, K);
-			const int units = ((O + 3) >> 2) * KB;
-			if (u < units) break;
-			u -= units;
-			off += O;
-		}
-		if (h == 3) return;
-		const int jb = u / KB;
-		kb = u - jb * KB;
-		A = s.dp2 + off + 4 * jb; lda = s.ld2;
-		B = s.hid + h * F + 4 * kb; ldb = s.ldh;
-		jv = O - 4 * jb; kv = F - 4 * kb;
-		out = 3 * F * Kd + 3 * F + (off + 4 * jb) * F + 4 * kb; outld = F;
-		bout = 3 * F * Kd + 3 * F + 11 * K * F + off + 4 * jb;
-	}
-	const size_t r0 = (size_t)blockIdx.x * BSR_HEADS_CHUNK;
-	const size_t r1 = r0 + BSR_HEADS_CHUNK < (size_t)s.n ? r0 + BSR_HEADS_CHUNK : (size_t)s.n;
-	// fp64: a product of two fp32 values is exact there, so a range's sum is rounded once, when it is stored
-	double acc[4][4], ab[4];
-#pragma unroll
-	for (int jj = 0; jj < 4; jj++) {
-		ab[jj] = 0.0;
-#pragma unroll
-		for (int kk = 0; kk < 4; kk++) acc[jj][kk] = 0.0;
-	}
-	for (size_t r = r0; r < r1; r++) {
-		const bsr_f32x4 av = *reinterpret_cast<const bsr_f32x4_a4*>(A + r * lda);
-		const bsr_f32x4 bv = *reinterpret_cast<const bsr_f32x4_a4*>(B + r * ldb);
-		const double aa[4] = {(double)av.x, (double)av.y, (double)av.z, (double)av.w};
-		const double bb[4] = {(double)bv.x, (double)bv.y, (double)bv.z, (double)bv.w};
-#pragma unroll
-		for (int jj = 0; jj < 4; jj++) {
-			ab[jj] = ab[jj] + aa[jj];
-#pragma unroll
-			for (int kk = 0; kk < 4; kk++) acc[jj][kk] = fma(aa[jj], bb[kk], acc[jj][kk]);
-		}
-	}
-	float* P = s.partials + (size_t)blockIdx.x * s.tot;
-#pragma unroll
-	for (int jj = 0; jj < 4; jj++) {
-		if (jj >= jv) continue;
-#pragma unroll
-		for (int kk = 0; kk < 4; kk++)
-			if (kk < kv) P[out + jj * outld + kk] = (float)acc[jj][kk];
-		if (kb == 0) P[bout + jj] = (float)ab[jj];
-	}
-}
-
-__global__ void __launch_bounds__(HEADS_SUM_BLOCK) k_heads_wsum(const float* __restrict__ partials, size_t chunks, int tot, int F,
-                                                                int K, bsr_heads_weight_grads dw)
-{
-	int t = blockIdx.x * HEADS_SUM_BLOCK + threadIdx.x;
-	if (t >= tot) return;
-	double sum = (double)partials[t];
-	for (size_t c = 1; c < chunks; c++) sum = sum + (double)partials[c * (size_t)tot + t];
-	const float s = (float)sum;
-	const int Kd = F + 4;
-	float* p;
-	int local;
-	if (t < 3 * F * Kd) {
-		const int h = t / (F * Kd);
-		local = t - h * F * Kd;
-		p = dw.head[h].w1;
-	} else if ((t -= 3 * F * Kd) < 3 * F) {
-		const int h = t / F;
-		local = t - h * F;
-		p = dw.head[h].b1;
-	} else if ((t -= 3 * F) < 11 * K * F) {
-		const int h = t < K * F ? 0 : (t < 8 * K * F ? 1 : 2);
-		local = t - heads_offset(h, K) * F;
-		p = dw.head[h].w2;
-	} else {
-		t -= 11 * K * F;
-		const int h = t < K ? 0 : (t < 8 * K ? 1 : 2);
-		local = t - heads_offset(h, K);
-		p = dw.head[h].b2;
-	}
-	if (p) p[local] = s;
-}
-
 // the checks both entry points share; fills the arguments
 static int heads_args(const char* who, int n, int F, int K, const float* feat, long long fs, const float* anchor,
                       const float* cam, const float* mask, const bsr_heads_weights* w, HeadsArgs& a)
@@ -411,26 +290,6 @@ static int heads_args(const char* who, int n, int F, int K, const float* feat, l
 	a.anchor = anchor; a.cam = cam; a.mask = mask;
 	a.w = *w;
 	return 0;
-}
-
-// a workgroup's LDS beyond the default 64 KiB has to be asked for (F and K near their limits in the row pass): once per
-// kernel and DEVICE, with the device's whole LDS, not per call.  Two host threads that meet here both ask, which is
-// harmless: the state is atomic and both store the same answer.
-#define HEADS_MAX_DEVICES 64
-template <typename Kern>
-static int heads_lds_limit(Kern kern, size_t bytes)
-{
-	static std::atomic<int> state[HEADS_MAX_DEVICES];   // (one array per kernel type) 0 not asked yet, 1 granted, -1 refused
-	if (bytes <= 64 * 1024) return 0;
-	int dev = 0;
-	if (hipGetDevice(&dev) != hipSuccess || dev < 0) return 1;
-	const bool tracked = dev < HEADS_MAX_DEVICES;
-	int st = tracked ? state[dev].load(std::memory_order_relaxed) : 0;
-	if (st == 0) {
-		st = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess ? 1 : -1;
-		if (tracked) state[dev].store(st, std::memory_order_relaxed);
-	}
-	return st < 0;
 }
 
 }  // namespace bsr
@@ -457,7 +316,7 @@ int bsr_anchor_heads_forward(int n, int F, int K, const float* feat, long long f
 	if (((uintptr_t)neural_opacity | (uintptr_t)color | (uintptr_t)scale_rot | (uintptr_t)maps) & 3)
 		return fail("%s: outputs must be 4-byte aligned", who);
 	const size_t lds = (size_t)(2 * F + 4) * HEADS_P * sizeof(float);
-	if (heads_lds_limit(k_heads_fwd, lds)) return fail("%s: cannot reserve %zu bytes of LDS", who, lds);
+	if (reserve_lds<k_heads_fwd>(who, lds)) return 1;
 	const unsigned blocks = (unsigned)(((long long)n + HEADS_T - 1) / HEADS_T);
 	hipLaunchKernelGGL(k_heads_fwd, dim3(blocks), dim3(HEADS_T), lds, (hipStream_t)stream, a, neural_opacity, color, scale_rot, maps);
 	if (hipGetLastError() != hipSuccess) return fail("%s: launch failed", who);
@@ -477,58 +336,23 @@ int bsr_anchor_heads_backward(int n, int F, int K, const float* feat, long long 
 	if (((uintptr_t)color | (uintptr_t)g_opacity | (uintptr_t)g_color | (uintptr_t)g_scale_rot | (uintptr_t)d_feat |
 	     (uintptr_t)d_anchor | (uintptr_t)d_offset_mask) & 3)
 		return fail("%s: upstreams and gradients must be 4-byte aligned", who);
-	bsr_heads_weight_grads grads = {};
-	bool sums = false;
-	if (dw) {
-		grads = *dw;
-		for (int h = 0; h < 3; h++) {
-			sums = sums || grads.head[h].w1 || grads.head[h].b1 || grads.head[h].w2 || grads.head[h].b2;
-			if (((uintptr_t)grads.head[h].w1 | (uintptr_t)grads.head[h].b1 | (uintptr_t)grads.head[h].w2 | (uintptr_t)grads.head[h].b2) & 3)
-				return fail("%s: weight gradients must be 4-byte aligned", who);
-		}
-	}
+	const MlpSegments grads = heads_segments(F, K, dw);
+	if (mlp_wgrad_check(who, grads)) return 1;
+	const bool sums = mlp_wgrad_asked(grads);
 	hipStream_t st = (hipStream_t)stream;
-	if (n == 0) {
-		for (int h = 0; h < 3 && sums; h++) {
-			const size_t O = h == 0 ? K : (h == 1 ? 7 * K : 3 * K);
-			float* p[4] = {grads.head[h].w1, grads.head[h].b1, grads.head[h].w2, grads.head[h].b2};
-			const size_t count[4] = {(size_t)F * (F + 4), (size_t)F, O * F, O};
-			for (int i = 0; i < 4; i++)
-				if (p[i] && hipMemsetAsync(p[i], 0, count[i] * sizeof(float), st) != hipSuccess) return fail("%s: memset failed", who);
-		}
-		return 0;
-	}
+	if (n == 0) return mlp_wgrad_zero(who, grads, st);
 	if (g_color && !color) return fail("%s: g_color needs the forward's color", who);
-	if (sums && !scratch) return fail("%s: the weight gradients need the scratch", who);
-	if ((uintptr_t)scratch & 15) return fail("%s: scratch must be 16-byte aligned", who);
-	const HeadsLayout l = heads_layout(n, F, K);
-	HeadsRowScratch rs = {};
-	float* base = (float*)scratch;
-	if (sums) {
-		rs.x = base; rs.hid = base + l.off_hid; rs.dp1 = base + l.off_dp1; rs.dp2 = base + l.off_dp2;
-		rs.ldx = l.ldx; rs.ldh = l.ldh; rs.ld2 = l.ld2;
-	}
+	const MlpWgradLayout l = heads_layout(n, F, K);
+	MlpRowScratch rs;
+	if (mlp_wgrad_carve(who, l, sums, scratch, rs)) return 1;
 	const size_t lds = (size_t)(3 * F + 8 + 7 * K) * HEADS_P * sizeof(float);
-	if (heads_lds_limit(k_heads_bwd_rows, lds)) return fail("%s: cannot reserve %zu bytes of LDS", who, lds);
+	if (reserve_lds<k_heads_bwd_rows>(who, lds)) return 1;
 	const unsigned blocks = (unsigned)(((long long)n + HEADS_T - 1) / HEADS_T);
 	hipLaunchKernelGGL(k_heads_bwd_rows, dim3(blocks), dim3(HEADS_T), lds, st, a, color, g_opacity, g_color, g_scale_rot, d_feat,
 	                   d_anchor, d_offset_mask, rs);
 	if (hipGetLastError() != hipSuccess) return fail("%s: launch failed", who);
 	if (!sums) return 0;
-	HeadsSumArgs s;
-	s.n = n; s.F = F; s.K = K; s.tot = l.tot;
-	s.x = rs.x; s.hid = rs.hid; s.dp1 = rs.dp1; s.dp2 = rs.dp2;
-	s.ldx = l.ldx; s.ldh = l.ldh; s.ld2 = l.ld2;
-	s.partials = base + l.off_partials;
-	const int KB = (F + 3) / 4;
-	const int units = ((3 * F + 3) / 4) * ((F + 4 + 3) / 4) + (((K + 3) / 4) + ((7 * K + 3) / 4) + ((3 * K + 3) / 4)) * KB;
-	hipLaunchKernelGGL(k_heads_wgrad, dim3((unsigned)l.chunks, (unsigned)((units + HEADS_SUM_BLOCK - 1) / HEADS_SUM_BLOCK)),
-	                   dim3(HEADS_SUM_BLOCK), 0, st, s);
-	if (hipGetLastError() != hipSuccess) return fail("%s: launch failed", who);
-	hipLaunchKernelGGL(k_heads_wsum, dim3((unsigned)((l.tot + HEADS_SUM_BLOCK - 1) / HEADS_SUM_BLOCK)), dim3(HEADS_SUM_BLOCK), 0, st,
-	                   s.partials, l.chunks, l.tot, F, K, grads);
-	if (hipGetLastError() != hipSuccess) return fail("%s: launch failed", who);
-	return 0;
+	return mlp_wgrad_sums(who, heads_products(F, K, rs, grads), grads, n, l, scratch, st);
 }
 
 }  // extern "C"

@@ -1,4 +1,6 @@
-// The layer-agnostic device functions of the row-per-lane MLP kernels (heads.hip, context.hip).
+// The layer-agnostic device functions of the row-per-lane MLP kernels (heads.hip, context.hip; anchor_state.hip takes the
+// sigmoid): the products of a row with a weight matrix, the cooperative stores of whole rows, the activations.  What the
+// row passes leave behind for the weight gradients is summed by mlp_wgrad.h.
 //
 // LANE MAPPING.  A lane is a row; a workgroup is ONE wave of 64 rows.  The row's vectors that are indexed by a loop
 // variable live in LDS as [index][lane] with a pitch of 65 floats: the lane's own column is read without bank conflicts,
@@ -17,14 +19,14 @@ namespace bsr {
 #define MLP_ROWS_NJ 8    // outputs accumulated at a time
 
 // a load whose address is uniform over the wave (biases, the camera): through the scalar cache
-typedef const float __attribute__((address_space(4))) heads_cf;
-__device__ __forceinline__ float uload(const float* p, int i) { return ((heads_cf*)p)[i]; }
+typedef const float __attribute__((address_space(4))) mlp_cf;
+__device__ __forceinline__ float uload(const float* p, int i) { return ((mlp_cf*)p)[i]; }
 // lane `l` (a constant) of a wave-wide vector of weights, as a scalar operand
 __device__ __forceinline__ float lane_value(float v, int l) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l)); }
 
-__device__ __forceinline__ float heads_relu(float p) { return p > 0.0f ? p : (p != p ? p : 0.0f); }
+__device__ __forceinline__ float mlp_relu(float p) { return p > 0.0f ? p : (p != p ? p : 0.0f); }
 
-__device__ __forceinline__ float heads_tanh(float x)
+__device__ __forceinline__ float mlp_tanh(float x)
 {
 	const float a = fabsf(x);
 	float t;
@@ -38,7 +40,7 @@ __device__ __forceinline__ float heads_tanh(float x)
 	return copysignf(t, x);
 }
 
-__device__ __forceinline__ float heads_sigmoid(float x) { return 1.0f / (1.0f + bsr_expf(-x)); }
+__device__ __forceinline__ float mlp_sigmoid(float x) { return 1.0f / (1.0f + bsr_expf(-x)); }
 
 // acc[j] = fmaf(x, weight in lane first + j * stride of wv, acc[j]) for the eight accumulators: the eight lane reads first,
 // then eight independent FMAs (one scalar register reused read by read costs wait states between every pair)
@@ -123,6 +125,15 @@ __device__ __forceinline__ void coop_store(float* dst, size_t ld, int C, const f
 	for (int idx = lane; idx < rows * C; idx += threads) {
 		const int r = idx / C, c = idx - r * C;
 		dst[(size_t)r * ld + c] = src[c * MLP_ROWS_P + r];
+	}
+}
+
+// dst[r * ld + c] = 0 for r < rows, c < C: coop_store's walk
+__device__ __forceinline__ void coop_zero(float* dst, size_t ld, int C, int rows, int lane, int threads = MLP_ROWS_T)
+{
+	for (int idx = lane; idx < rows * C; idx += threads) {
+		const int r = idx / C, c = idx - r * C;
+		dst[(size_t)r * ld + c] = 0.0f;
 	}
 }
 
