@@ -5,6 +5,9 @@
 // otherwise leave those CPU tests green).  Also the backward walks' cross-lane sum networks (bwd_sums.h) on given
 // per-lane inputs, for tests/test_bwd_sums_gpu.py.  Built by tests/native/Makefile into libbsr_pure_functions.so; driven by
 // tests/test_round6_gpu.py and tests/test_bwd_sums_gpu.py through ctypes.  Nothing here is part of the product library.
+// (The shared workgroup scans of wg_scan.h, the grid-wide fp64 sum of grid_sum.h and the weight-gradient sums of
+// mlp_wgrad.{h,hip} have a unit of their own beside this one, shared_pieces.hip -> libbsr_shared_pieces.so, built with the
+// product's own flags: tests/test_wg_scan_gpu.py, test_grid_sum_gpu.py and test_mlp_wgrad_direct_gpu.py.)
 #include "../../bloomscene_amd/csrc/tile_common.h"
 #include "../../bloomscene_amd/csrc/bwd_sums.h"
 #include "../../bloomscene_amd/csrc/scratch.h"
